@@ -2,7 +2,15 @@
 """bench.py -- throughput of the UniFrac pair reduction (the hot path) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3] [--precision fixed32]
-                    [--scaling weak|strong] [--no-secondary] [--no-cpu-baseline] [--no-live-traffic]
+                    [--dump-outputs DIR] [--full [--scaling weak|strong] [--no-secondary] [--no-cpu-baseline]
+                    [--no-live-traffic] [--no-end-to-end]]
+
+A plain run does what the headline figure needs and nothing else: it sets the problem up, runs W untimed and K timed
+steps, writes the last timed step's result if `--dump-outputs DIR` is given (DIR/distances.npy, float64: the distances
+the step handed its caller, in IterPairs order; of more than 7.5 million a fixed, seeded sample) and prints the primary
+record.  Everything else below -- `secondary`, `reference_width`, `sparse_regime`, `cpu_baseline`, `end_to_end`, the live
+counter passes, and at N > 1 `strong_base`, `weak_scaling` and the secondary C5 -- takes runs of its own and is measured
+under `--full` only.
 
 A "step" is one pass of the hot path over one batch of synthetic input: the pair
 kernels over this rank's row shard of the staged matrix (already resident in HBM)
@@ -19,7 +27,7 @@ and carries the weak-scaled C3 (samples = 4096*sqrt(N), every GPU keeps C3's pai
 it as `weak_scaling`; `--scaling weak|strong` with a `--workload` runs just that.  `value` is
 all ranks' pairs / max-over-ranks time.
 
-`secondary` carries the other claimed numbers under the same clock, each with its own
+`secondary` (`--full`) carries the other claimed numbers under the same clock, each with its own
 `config.workload`, `dtype`, `ms_per_step` and `roofline`:
   N = 1: C3 in EXACT64 (the reference's binary64 roundings; also `reference_width` of the
          primary record), C3 unweighted (int8 matrix cores), C2 (BASELINE configs[1]), C4 and
@@ -30,11 +38,11 @@ all ranks' pairs / max-over-ranks time.
 
 Prints ONE JSON line on rank 0; `roofline` describes the dominant kernel, timed with HIP
 events around every launch of the timed region on the stream it is launched on
-(ff_plan_run_timed / ff_plan_timing_collect).  At N = 1 the primary record's `roofline.traffic`
+(ff_plan_run_timed / ff_plan_timing_collect).  At N = 1 under `--full` the primary record's `roofline.traffic`
 -- the dominant kernel's bytes beyond L2 per launch -- is counted on the box the bench runs on:
 with every timing done, two child runs of this script under `rocprofv3 --pmc` (FETCH_SIZE,
-WRITE_SIZE: separate passes, counters only); `--no-live-traffic`, a bench that is itself under a
-profiler, or a failed pass fall back on the committed counts of profiles/traffic.json and say so.
+WRITE_SIZE: separate passes, counters only); a plain run, `--no-live-traffic`, a bench that is itself under a
+profiler, or a failed pass carry the committed counts of profiles/traffic.json and say so.
 """
 import argparse
 import json
@@ -472,12 +480,30 @@ def with_traffic(roofline, traffic):
     return roofline
 
 
-def measure(ctx, cfg, nodes, weighted, precision, steps, warmup, event_every=1):
+DUMP_MAX_ELEMS = 7500000   # 60 MB of float64
+
+
+def dump_outputs(directory, res, max_elems=DUMP_MAX_ELEMS):
+    """--dump-outputs: what the last timed step handed its caller -- the distances in IterPairs order, one float64 per
+    pair -- as <directory>/distances.npy.  Of more than max_elems the file holds a sample that is the same in every run:
+    the index range is cut into max_elems equal strata and a generator of fixed seed draws one index in each."""
+    import torch
+
+    os.makedirs(directory, exist_ok=True)
+    n = res.numel()
+    if n > max_elems:
+        edges = np.arange(max_elems + 1, dtype=np.int64) * n // max_elems
+        idx = np.random.default_rng(0xD157).integers(edges[:-1], edges[1:])
+        res = res[torch.from_numpy(idx).to(res.device)]
+    np.save(os.path.join(directory, "distances.npy"), res.cpu().numpy().astype(np.float64, copy=False))
+
+
+def measure(ctx, cfg, nodes, weighted, precision, steps, warmup, event_every=1, dump_dir=None):
     """Stages the problem on this rank, runs `warmup` untimed and `steps` timed steps, returns
     rank 0's entry (None on other ranks).  event_every: the HIP-event pair that times the dominant kernel
     brackets every launch (1) or every event_every-th launch of the timed region -- for steps of a few
     microseconds, where two event records per launch cost as much as the launch itself (C2: 6.4 us per step
-    without them, about 10 with)."""
+    without them, about 10 with).  dump_dir: rank 0 writes the last timed step's result there (dump_outputs)."""
     import frackyfrac_amd as ff
     from frackyfrac_amd.distributed import ShardedRun
 
@@ -510,6 +536,8 @@ def measure(ctx, cfg, nodes, weighted, precision, steps, warmup, event_every=1):
     barrier(ctx)
     elapsed = time.perf_counter() - t0
     kernel_ms_total, rare_ms_total, launches = run.timing_collect_parts()
+    if dump_dir and ctx.rank == 0:
+        dump_outputs(dump_dir, res)
     per_rank = None
     if ctx.world > 1:
         # what a post-mortem of the first multi-GPU run needs, from every rank: its own clock around the
@@ -586,27 +614,34 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # (defaults: about a second of GPU time in the timed region, so that an outside sampler of GPU activity sees it)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="C3", help="C2|C3|C4|C5 or SAMPLESxLEAVES[@DENSITY] (e.g. 2048x5000, 8192x50000@0.01)")
     ap.add_argument("--precision", default="fixed32", choices=["auto", "fixed32", "exact64"])
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"],
                     help="N > 1: weak = samples grow as sqrt(N) (per-GPU pairs fixed), strong = the workload's own size; "
                          "not given (and the default workload): BASELINE configs[3] -- C4, 16,384 samples, pair tiles over "
-                         "the N GPUs, strong by construction -- as the primary line and the weak-scaled C3 beside it")
+                         "the N GPUs, strong by construction -- as the primary line and, under --full, the weak-scaled C3 beside it")
     ap.add_argument("--unweighted", action="store_true")
     ap.add_argument("--lengths", default="generator", choices=["generator", "lognormal"],
                     help="branch lengths: the generator's multiples of 1/1024, or log-normal (sigma 1.5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's distances to DIR/distances.npy (float64; of more than "
+                         "7.5 million a fixed, seeded sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the primary record, everything else the bench measures in runs of their own: secondary, "
+                         "reference_width, sparse_regime, cpu_baseline, end_to_end, the live counter passes; N > 1: strong_base, "
+                         "weak_scaling and the secondary C5 (the --no-... options below leave parts of it out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="only the primary line")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="roofline.traffic from profiles/traffic.json only (default at N = 1: two child runs under "
+                    help="roofline.traffic from profiles/traffic.json only (--full at N = 1: two child runs under "
                          "rocprofv3 --pmc measure it on this box once the timings are done)")
     ap.add_argument("--secondary-steps", type=int, default=5)
     ap.add_argument("--cpu-budget", type=float, default=18.0)
-    ap.add_argument("--end-to-end", action="store_true", help="(kept for old command lines: end to end is in the default line)")
+    ap.add_argument("--end-to-end", action="store_true", help="(kept for old command lines: end to end is in the --full line)")
     ap.add_argument("--no-end-to-end", action="store_true",
-                    help="skip `end_to_end` (default at N = 1 on the default workload: ff_unifrac_dists through host buffers, "
+                    help="skip `end_to_end` (--full at N = 1 on the default workload: ff_unifrac_dists through host buffers, "
                          "and the frcfrc executable on C3 and C4 as files)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="N > 1 ranks that all use GPU 0 with gloo as control plane (RCCL refuses two ranks on "
@@ -664,10 +699,10 @@ def main():
         cfg["lengths"] = "lognormal"
     # (steps of a few microseconds -- the unweighted matrix-core kernels -- carry the event pair on every 8th launch)
     primary = measure(ctx, cfg, nodes, weighted, args.precision, args.steps, args.warmup,
-                      event_every=1 if weighted or args.precision == "exact64" else 8)
+                      event_every=1 if weighted or args.precision == "exact64" else 8, dump_dir=args.dump_outputs)
     weak_entry = None
     strong_base = None
-    if lead_c4:
+    if lead_c4 and args.full:
         # the honest base of the strong curve: the SAME problem (C4) on ONE GPU of this node, this build, this run --
         # rank 0 alone reduces the whole triangle while the others wait at the barrier below (C3's pairs cost 1.6 %
         # more each than C4's on one GPU, so value(N) / (N * value(1)) with the N = 1 line's C3 would flatter the curve)
@@ -691,7 +726,7 @@ def main():
             weak_entry.pop("_active_fraction", None)
 
     e2e = None
-    want_e2e = rank == 0 and world == 1 and not args.no_end_to_end and not ctx.rehearse
+    want_e2e = args.full and rank == 0 and world == 1 and not args.no_end_to_end and not ctx.rehearse
     if want_e2e:
         # Host-buffer entry point (ff_unifrac_dists): upload of the flat nodes over PCIe,
         # staging, the pair kernels and the download of the distances.  Never `value`.
@@ -754,12 +789,12 @@ def main():
                                  "text_stream_ms": e2e_text * 1e3, "text_stream_bytes": e2e_text_bytes,
                                  "text_stream_note": "ff_unifrac_text_stream on the same host arrays: + the formatter on the device, the "
                                                      "distances come down as the lines the reference prints; the callback only counts"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(nodes, weighted, args.cpu_budget)
 
     # ---- secondary: the other claimed numbers, same clock ------------------------------------
-    if (not args.no_secondary and args.workload == "C3" and not args.unweighted and args.precision == "fixed32" and
-            args.lengths == "generator" and (world == 1 or lead_c4)):
+    if (args.full and not args.no_secondary and args.workload == "C3" and not args.unweighted and
+            args.precision == "fixed32" and args.lengths == "generator" and (world == 1 or lead_c4)):
         sec = []
         k, w = max(1, min(args.secondary_steps, args.steps)), 1
         if world == 1:
@@ -795,8 +830,8 @@ def main():
             for e in sec:
                 e.pop("_active_fraction", None)
             out["secondary"] = sec
-    if (rank == 0 and world == 1 and not args.no_secondary and args.workload == "C3" and not args.unweighted and
-            args.precision == "fixed32" and args.lengths == "generator"):
+    if (args.full and rank == 0 and world == 1 and not args.no_secondary and args.workload == "C3" and
+            not args.unweighted and args.precision == "fixed32" and args.lengths == "generator"):
         # Where real tables live: BASELINE configs[4]'s tree and sample count at 1 % and 0.2 % leaf density
         # instead of its 5-10 %.  The engine compacts the branches no sample reaches, reduces the rows few samples reach
         # over the pairs that both have them (pair_low_kernel: 97-99 % of the rows here) and keeps the rest
@@ -832,7 +867,7 @@ def main():
             except Exception as e:  # (the line must come out)
                 e2e_runs.append({"workload": wl, "error": "%s: %s" % (type(e).__name__, e)})
         out.setdefault("end_to_end", {})["frcfrc"] = e2e_runs
-    if rank == 0 and world == 1 and not args.no_live_traffic and not ctx.rehearse:
+    if args.full and rank == 0 and world == 1 and not args.no_live_traffic and not ctx.rehearse:
         # last, with every timing of the line done: the primary kernel's traffic beyond L2 as this box's counters see it
         if under_a_profiler():
             out["roofline"]["traffic_note"] = "run under a profiler: no live counter passes"

@@ -38,6 +38,28 @@ def test_self_launch_relays_the_ranks_exit_code_and_keeps_the_parent_off_the_gpu
     assert "parent imported torch: False" in r.stderr
 
 
+def test_dump_outputs_writes_everything_or_the_same_sample_every_time(tmp_path):
+    """bench.py --dump-outputs: up to the cap the whole result as float64; above it one element of each of `cap` equal
+    strata of the index range, the same ones in every run."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    res = torch.arange(1000, dtype=torch.float64) / 1000.0
+    bench.dump_outputs(str(tmp_path / "all"), res)
+    got = np.load(tmp_path / "all" / "distances.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, res.numpy())
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), res, max_elems=64)
+    a, b = (np.load(tmp_path / d / "distances.npy") for d in ("a", "b"))
+    assert a.dtype == np.float64 and a.shape == (64,) and np.array_equal(a, b)
+    k = np.rint(a * 1000.0).astype(np.int64)      # (the values are their own indices)
+    edges = np.arange(65) * 1000 // 64
+    assert np.all(edges[:-1] <= k) and np.all(k < edges[1:])
+    assert bench.DUMP_MAX_ELEMS * 8 <= 64e6
+
+
 def _fake_rocprofv3(tmp_path, body):
     """A stand-in for rocprofv3 on PATH: parses `--pmc NAME` and `-d DIR` and runs `body` (python source with NAME and
     DIR in scope) instead of profiling anything."""

@@ -56,8 +56,40 @@ def test_self_launch_runs_two_ranks_and_prints_one_line():
     assert out["scaling"] == "weak" and out["config"]["pairs"] == 1088 * 1087 // 2
 
 
+def test_plain_run_is_the_primary_record_alone_and_dumps_the_last_steps_distances(tmp_path):
+    """Without --full the line is the primary record: nothing that takes runs of its own (secondary entries, CPU baseline,
+    end to end, live counter passes).  --dump-outputs leaves the last timed step's distances, one float64 per pair in
+    IterPairs order, and they are the oracle's on the same seeded inputs within FIXED32's bar."""
+    import numpy as np
+
+    import bench
+    from frackyfrac_amd import synth
+    from oracle import oracle as O
+
+    d = tmp_path / "dump"
+    out, _ = run_bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "768x1500", "--dump-outputs", str(d))
+    assert out["metric"] and out["unit"] == "pairs/s" and out["higher_is_better"] is True and out["dtype"] == "u32"
+    assert out["n_gpus"] == 1 and out["steps"] == 3 and out["roofline"]["launches"] == 3
+    pairs = 768 * 767 // 2
+    assert out["config"]["pairs"] == pairs and abs(out["value"] - pairs / (out["ms_per_step"] * 1e-3)) <= 1e-6 * out["value"]
+    for k in ("secondary", "reference_width", "sparse_regime", "cpu_baseline", "end_to_end"):
+        assert k not in out, k
+    assert "traffic_note" not in out["roofline"] and "fetch_size_kib" not in out["roofline"]
+    assert sorted(p.name for p in d.iterdir()) == ["distances.npy"]
+    got = np.load(d / "distances.npy")
+    assert got.dtype == np.float64 and got.shape == (pairs,)
+    ctx = bench.Ctx()
+    ctx.rank, ctx.world = 0, 1
+    cfg, _ = bench.make_problem(ctx, "768x1500")
+    tree, ptr, idx, val = synth.make(cfg["n_samples"], cfg["n_leaves"], cfg["density"], cfg["seed"])
+    ft = O.FlatTree(tree.names, tree.branch_len, tree.size, tree.parent)
+    ip, on = O.flatten_samples(ft, ptr, idx, val, 0)
+    want = O.unifrac_dists(ip, on, ft.dist, True)
+    assert np.all(np.abs(got - want) <= 1e-6 * np.abs(want))
+
+
 def test_single_gpu_line_carries_the_secondary_entries():
-    out, _ = run_bench("--steps", "3", "--warmup", "1", "--secondary-steps", "2", "--cpu-budget", "3")
+    out, _ = run_bench("--full", "--steps", "3", "--warmup", "1", "--secondary-steps", "2", "--cpu-budget", "3")
     assert out["n_gpus"] == 1 and out["dtype"] == "u32" and out["config"]["workload"].startswith("C3:")
     # (three quarters of C3's staged rows are reduced by pair_low_kernel: the fraction of the full 2*B count passes 1; each
     # kernel on its own rows is in `parts`, from the event the plan records between the two launches -- the matrix rows'
@@ -156,7 +188,7 @@ def test_default_multi_gpu_line_leads_with_c4_strong_and_carries_the_weak_one():
     """`python bench.py --gpus N` as the driver starts it (no --scaling, no --workload): the line leads with BASELINE
     configs[3] -- C4 at its stated size, pair tiles over the N ranks, "scaling": "strong" -- and carries the
     weak-scaled C3 beside it; C5 is the secondary entry.  Rehearsed with two ranks on the one GPU."""
-    out, _ = run_bench("--gpus", "2", "--rehearse-on-one-gpu", "--steps", "2", "--warmup", "1", "--secondary-steps", "1",
+    out, _ = run_bench("--full", "--gpus", "2", "--rehearse-on-one-gpu", "--steps", "2", "--warmup", "1", "--secondary-steps", "1",
                        "--no-cpu-baseline")
     assert out["n_gpus"] == 2 and out["scaling"] == "strong"
     assert out["config"]["workload"].startswith("C4:") and out["config"]["pairs"] == 16384 * 16383 // 2

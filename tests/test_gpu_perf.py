@@ -28,7 +28,7 @@ def test_c2_pass_takes_microseconds_not_tens_of_them():
 
 
 def test_graded_planes_cost_less_than_two_sweeps_and_exact_unweighted_half_of_the_weighted_walk():
-    out, _ = run_bench("--steps", "3", "--warmup", "1", "--secondary-steps", "2", "--no-cpu-baseline", "--no-live-traffic")
+    out, _ = run_bench("--full", "--steps", "3", "--warmup", "1", "--secondary-steps", "2", "--no-cpu-baseline", "--no-live-traffic")
     sec = out["secondary"]
     assert sec[1]["ms_per_step"] < sec[5]["ms_per_step"] < 2.0 * sec[1]["ms_per_step"]   # (two sweeps cost 1.85 x)
     assert sec[6]["ms_per_step"] < 0.7 * sec[0]["ms_per_step"]       # pair_exact_unw_kernel 10 ms, pair_exact64_skip_kernel 21
@@ -40,7 +40,7 @@ def test_figures_of_record_have_not_gone_backwards():
     unsplit) and its matrix part on its own rows (0.87), weighted EXACT64 at C3 (20.8-21.5 ms; 30.1 before
     pair_exact64_skip_kernel), the exact unweighted kernel (9.9-10.0 ms; 30 before it existed), C4 and C5 on one GPU
     (1.9 / 3.0 of the full count)."""
-    out, _ = run_bench("--steps", "20", "--warmup", "3", "--secondary-steps", "3", "--no-cpu-baseline", "--no-live-traffic")
+    out, _ = run_bench("--full", "--steps", "20", "--warmup", "3", "--secondary-steps", "3", "--no-cpu-baseline", "--no-live-traffic")
     sec = out["secondary"]
     assert out["roofline"]["frac"] >= 1.3, out["roofline"]["frac"]
     assert out["roofline"]["parts"][0]["frac"] >= 0.70, out["roofline"]["parts"]
@@ -55,7 +55,7 @@ def test_live_counter_traffic_is_measured_on_this_box_and_agrees_with_the_commit
     the committed figure of profiles/traffic.json beside it -- same build, same schedule: the same traffic within the
     counters' noise.  Here and not under `-m gpu`: a box whose profiler refuses a counter must not turn the parity
     record red (the line then carries `traffic_note` and the committed figure: test_gpu_bench.py)."""
-    out, _ = run_bench("--steps", "3", "--warmup", "1", "--no-secondary", "--no-cpu-baseline", "--no-end-to-end")
+    out, _ = run_bench("--full", "--steps", "3", "--warmup", "1", "--no-secondary", "--no-cpu-baseline", "--no-end-to-end")
     rl, hbm = out["roofline"], out["roofline"]["hbm"]
     assert rl["traffic_source"].startswith("live on this box"), rl.get("traffic_note")
     assert rl["fetch_size_kib"] > 0 and rl["write_size_kib"] > 0
@@ -67,7 +67,7 @@ def test_live_counter_traffic_is_measured_on_this_box_and_agrees_with_the_commit
 def test_frcfrc_on_c4_takes_a_second_not_six():
     """6.5 s with the reference's default flags until round 5 (the formatter on one host thread); 0.76 s measured with
     the formatter on the device and the host threads defaulting to the CPU quota."""
-    out, _ = run_bench("--steps", "3", "--warmup", "1", "--no-secondary", "--no-cpu-baseline", "--no-live-traffic")
+    out, _ = run_bench("--full", "--steps", "3", "--warmup", "1", "--no-secondary", "--no-cpu-baseline", "--no-live-traffic")
     c4 = [e for e in out["end_to_end"]["frcfrc"] if e["workload"] == "C4"][0]
     default = [r for r in c4["runs"] if r["flags"] == "(default)"][0]
     assert default["wall_s"] <= 2.0, default
