@@ -31,6 +31,7 @@ using namespace ff::sched;
 #include "ff_kernels_exact_unw.hpp"
 #include "ff_kernels_exact_w.hpp"
 #include "ff_kernels_low.hpp"
+#include "ff_kernels_low_unw.hpp"
 
 }  // namespace
 
@@ -43,6 +44,30 @@ using namespace ff::sched;
 // (rebuilt by ff_plan_set_shard; the staged matrix does not depend on the shard)
 
 
+namespace {
+
+// A split plan's blocks of pairs (pair_low_kernel, pair_low_unw_kernel) that hold a row of the shard -- sample blocks
+// bi x bj <= bi -- and the shard's slots of their sums.
+int schedule_low_tiles(ff_plan *pl, char *err, size_t errlen)
+{
+    const ff_plan_info &inf = pl->info;
+    const int64_t N = inf.n_samples, n_slots = inf.slot_end - inf.slot_begin;
+    free_and_null(pl->d_low_tiles);
+    free_and_null(pl->d_mlow);
+    pl->n_low_tiles = 0;
+    if (!pl->split || n_slots <= 0) return FF_OK;
+    std::vector<LowTile> lt;
+    for (int64_t bi = inf.row_begin / pl->low_tile; bi * pl->low_tile < std::min(inf.row_end, N); ++bi)
+        for (int64_t bj = 0; bj <= bi; ++bj) lt.push_back({(int32_t)bi, (int32_t)bj});
+    pl->n_low_tiles = (int)lt.size();
+    FF_HIP(hipMalloc(&pl->d_low_tiles, sizeof(LowTile) * std::max<size_t>(lt.size(), 1)));
+    if (!lt.empty()) FF_HIP(hipMemcpy(pl->d_low_tiles, lt.data(), sizeof(LowTile) * lt.size(), hipMemcpyHostToDevice));
+    FF_ALLOC(pl->d_mlow, sizeof(uint32_t) * (size_t)n_slots, "the rare rows' sums");
+    return FF_OK;
+}
+
+}  // namespace
+
 int schedule_sad(ff_plan *pl, char *err, size_t errlen)
 {
     ff_plan_info &inf = pl->info;
@@ -51,18 +76,9 @@ int schedule_sad(ff_plan *pl, char *err, size_t errlen)
     free_and_null(pl->d_item_ptr);
     free_and_null(pl->d_num);
     free_and_null(pl->d_stamps);
-    free_and_null(pl->d_low_tiles);
-    free_and_null(pl->d_mlow);
-    pl->n_low_tiles = 0;
-    if (pl->split && n_slots > 0) {
-        // the blocks of pairs of pair_low_kernel that hold a row of the shard: sample blocks bi x bj <= bi
-        std::vector<LowTile> lt;
-        for (int64_t bi = inf.row_begin / pl->low_tile; bi * pl->low_tile < std::min(inf.row_end, N); ++bi)
-            for (int64_t bj = 0; bj <= bi; ++bj) lt.push_back({(int32_t)bi, (int32_t)bj});
-        pl->n_low_tiles = (int)lt.size();
-        FF_HIP(hipMalloc(&pl->d_low_tiles, sizeof(LowTile) * std::max<size_t>(lt.size(), 1)));
-        if (!lt.empty()) FF_HIP(hipMemcpy(pl->d_low_tiles, lt.data(), sizeof(LowTile) * lt.size(), hipMemcpyHostToDevice));
-        FF_ALLOC(pl->d_mlow, sizeof(uint32_t) * (size_t)n_slots, "the rare rows' sums");
+    {
+        const int rc = schedule_low_tiles(pl, err, errlen);
+        if (rc != FF_OK) return rc;
     }
     std::vector<Tile> tiles;
     build_tiles(N, inf.row_begin, inf.row_end, TILE_I, TILE_J, true, &tiles);
@@ -146,6 +162,10 @@ int schedule_mfma(ff_plan *pl, char *err, size_t errlen)
     pl->m_small = false;
     pl->n_stiles = 0;
     pl->n_mitems = 0;
+    {
+        const int rc = schedule_low_tiles(pl, err, errlen);
+        if (rc != FF_OK) return rc;
+    }
     const int64_t slabs = pl->m_ldb / M_KSLAB;
     const int G = inf.n_compute_units * M_WGS_PER_CU;  // one 8-wave workgroup per CU
     pl->n_mgroups = G;
@@ -163,14 +183,14 @@ int schedule_mfma(ff_plan *pl, char *err, size_t errlen)
             const int64_t w = std::min<int64_t>(std::min<int64_t>(i0 + S_TILE, inf.row_end) - 1, N);  // valid columns: j < w
             n_st += (w + S_TILE - 1) / S_TILE;  // (= I + 1, or I for a last block of one row)
         }
-        int64_t big_tiles = 0;
-        for (int64_t i0 = inf.row_begin / M_TILE_I * M_TILE_I; i0 < inf.row_end; i0 += M_TILE_I)
-            big_tiles += (std::min<int64_t>(std::min<int64_t>(i0 + M_TILE_I, inf.row_end) - 1, N) + M_TILE_J - 1) / M_TILE_J;
+        const int64_t big_tiles = mfma_big_tiles(N, inf.row_begin, inf.row_end);
         const int force = env_int("FF_MFMA_SMALL", -1);
         const bool fits = n_st > 0 && pl->m_digits <= S_MAX_DIGITS && n_st < ((int64_t)1 << 30) &&
                           pl->m_ldb * pl->m_digits <= S_TABLE_BYTES;  // (its digit planes live in LDS)
-        const bool small = fits && (force >= 0 ? force != 0
-                                               : big_tiles < G && (double)n_st * 2.0 * (double)slabs <= S_MAX_WORK);
+        // (a plan whose rare rows are reduced apart stays on the big kernel, whatever the shard: every exit of that
+        // one takes 2 mlow off U, the small kernel does not know the term)
+        const bool small = fits && !pl->split && (force >= 0 ? force != 0
+                                                             : big_tiles < G && (double)n_st * 2.0 * (double)slabs <= S_MAX_WORK);
         if (small) {
             pl->m_small = true;
             pl->n_stiles = (int)n_st;
@@ -560,6 +580,17 @@ int plan_run_impl(ff_plan *pl, hipStream_t st, double *d_out, bool timed, char *
         if (!fused && (!pl->mfma || pl->m_any_atomic))
             FF_HIP(hipMemsetAsync(pl->d_num, 0, sizeof(uint32_t) * (size_t)n_slots, st));
         if (timed) FF_HIP(hipEventRecord(ev0, st));
+        if (pl->mfma && pl->split && pl->n_low_tiles > 0) {
+            // the rare rows of an unweighted plan first: the matrix-core path's exits read their sums.  (Inside the timed
+            // region; the parts event stands behind it: ff_plan_timing_collect_parts.)
+            static_assert(sizeof(LOW_TILES) / sizeof(int) == 5, "one instance of pair_low_unw_kernel per block side");
+            auto low = pl->low_tile == 128 ? pair_low_unw_kernel<128> : pl->low_tile == 112 ? pair_low_unw_kernel<112> :
+                       pl->low_tile == 96 ? pair_low_unw_kernel<96> : pl->low_tile == 80 ? pair_low_unw_kernel<80> : pair_low_unw_kernel<64>;
+            low<<<dim3((unsigned)pl->n_low_tiles), dim3(LOW_THREADS), 0, st>>>(
+                pl->d_low_ptr, pl->d_low_ent16, pl->d_low_k, pl->d_low_bits, pl->low_words, pl->low_rows + 1, pl->d_low_tiles,
+                inf.n_samples, inf.row_begin, inf.row_end, inf.slot_begin, pl->d_mlow);
+            if (timed) FF_HIP(hipEventRecord(ev_mid, st));
+        }
         if (pl->mfma && pl->m_small) {
             FinishArgs none = fin;
             none.out = nullptr;  // null: integer sums into num[]
@@ -623,7 +654,7 @@ int plan_run_impl(ff_plan *pl, hipStream_t st, double *d_out, bool timed, char *
                 <<<dim3((unsigned)pl->n_workgroups), dim3((unsigned)pl->waves_per_wg * 64), pl->lds_bytes, st>>>(
                 pl->d_QT, inf.ld, pl->d_items, pl->d_item_ptr, pl->d_num, pl->plane_stride, inf.row_begin, inf.row_end,
                 inf.slot_begin, pl->d_stamps, SYNC_TRIPS);
-        if (pl->split && pl->n_low_tiles > 0) {  // (inside the timed region: it is part of the pair reduction)
+        if (!pl->mfma && pl->split && pl->n_low_tiles > 0) {  // (inside the timed region: it is part of the pair reduction)
             if (timed) FF_HIP(hipEventRecord(ev_mid, st));
             static_assert(sizeof(LOW_TILES) / sizeof(int) == 5, "one instance of pair_low_kernel per block side");
             auto low = pl->low_tile == 128 ? pair_low_kernel<128> : pl->low_tile == 112 ? pair_low_kernel<112> :

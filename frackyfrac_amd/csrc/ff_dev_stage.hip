@@ -407,6 +407,58 @@ int compact_branches(StageCtx &x, char *err, size_t errlen)
     return FF_OK;
 }
 
+// The rare rows of a split plan (pl->split, low_tile, low_rows are set; low_of: branch id -> rare row or -1) grouped by
+// sample block: counts -> positions -> entries -> row bitmaps.  Weighted: (sample, value) pairs at the scale e for
+// pair_low_kernel; unweighted: the samples' 16-bit places alone for pair_low_unw_kernel (k by rare row is the caller's).
+int build_low_index(StageCtx &x, const int32_t *low_of, int64_t Rl, int e, char *err, size_t errlen)
+{
+    FF_STAGE_NAMES;
+    const int nb = (int)((N + pl->low_tile - 1) / pl->low_tile);
+    pl->low_blocks = nb;
+    pl->low_words = (Rl + 63) / 64;
+    const int64_t rows1 = Rl + 1;
+    const size_t cells = (size_t)rows1 * (size_t)nb;
+    FF_ALLOC(pl->d_low_ptr, sizeof(uint32_t) * cells, "the rare rows' index");
+    FF_HIP(hipMemset(pl->d_low_ptr, 0, sizeof(uint32_t) * cells));
+    low_sums_counts_kernel<<<dim3((unsigned)N), dim3(256)>>>(d_indptr, d_ids, d_abnd, d_len, e, low_of, rows1, pl->low_tile, pl->d_low_ptr,
+                                                              nullptr, nullptr);
+    Scratch<uint32_t> totals, cursor;
+    FF_HIP(totals.alloc((size_t)nb + 1));
+    FF_HIP(cursor.alloc(cells));
+    FF_HIP(hipMemset(cursor.p, 0, sizeof(uint32_t) * cells));
+    // per block: exclusive prefix over its rows1 positions (the last one becomes the block's total), then the
+    // blocks' bases
+    scan_segments_kernel<<<dim3((unsigned)nb), dim3(1024)>>>(pl->d_low_ptr, rows1, rows1, totals.p);
+    FF_HIP(hipGetLastError());
+    std::vector<uint32_t> h_tot((size_t)nb), h_base((size_t)nb + 1, 0u);
+    FF_HIP(hipMemcpy(h_tot.data(), totals.p, sizeof(uint32_t) * (size_t)nb, hipMemcpyDeviceToHost));
+    uint64_t run = 0;
+    for (int k = 0; k < nb; ++k) {
+        h_base[(size_t)k] = (uint32_t)run;
+        run += h_tot[(size_t)k];
+    }
+    if (run >= 0xFFFFFFF0ull) return ff::fail(FF_ERR_INTERNAL, err, errlen, "too many rare-row entries");
+    const uint32_t n_entries = (uint32_t)run;
+    FF_HIP(hipMemcpy(totals.p, h_base.data(), sizeof(uint32_t) * (size_t)nb, hipMemcpyHostToDevice));
+    low_add_base_kernel<<<dim3((unsigned)((cells + 255) / 256)), dim3(256)>>>(pl->d_low_ptr, rows1, nb, totals.p);
+    if (weighted) {
+        FF_ALLOC(pl->d_low_ent, sizeof(uint2) * ((size_t)n_entries + 4), "the rare rows' entries");
+        FF_HIP(hipMemset(pl->d_low_ent + n_entries, 0, sizeof(uint2) * 4));  // (spare: pair_low_kernel loads four at a time, and adds the zeros)
+        low_fill_kernel<<<dim3((unsigned)N), dim3(256)>>>(d_indptr, d_ids, d_abnd, d_len, e, low_of, rows1, pl->low_tile, pl->d_low_ptr, cursor.p,
+                                                           pl->d_low_ent);
+    } else {
+        FF_ALLOC(pl->d_low_ent16, sizeof(uint16_t) * (size_t)low_unw_alloc_entries(n_entries), "the rare rows' entries");
+        FF_HIP(hipMemset(pl->d_low_ent16 + n_entries, 0, sizeof(uint16_t) * LOW_UNW_SPARE));  // (spare: ff_schedule.hpp)
+        low_fill_unw_kernel<<<dim3((unsigned)N), dim3(256)>>>(d_indptr, d_ids, low_of, rows1, pl->low_tile, pl->d_low_ptr, cursor.p, pl->d_low_ent16);
+    }
+    FF_ALLOC(pl->d_low_bits, sizeof(unsigned long long) * (size_t)nb * (size_t)pl->low_words, "the rare rows' bitmaps");
+    low_bits_kernel<<<dim3((unsigned)pl->low_words, (unsigned)nb), dim3(64)>>>(pl->d_low_ptr, Rl, rows1, pl->low_words, pl->d_low_bits);
+    FF_HIP(hipGetLastError());
+    FF_HIP(hipDeviceSynchronize());  // (the scratch arrays go out of scope)
+    inf.staged_bytes += 4.0 * (double)cells + (weighted ? 8.0 : 2.0) * (double)n_entries + 8.0 * (double)nb * (double)pl->low_words;
+    return FF_OK;
+}
+
 // FIXED32 unweighted on the matrix cores: presence / digit planes, sample-major, and the MFMA schedule.
 int stage_for_mfma(StageCtx &x, char *err, size_t errlen)
 {
@@ -422,13 +474,124 @@ int stage_for_mfma(StageCtx &x, char *err, size_t errlen)
     if (!x.branch_used.empty())
         for (int64_t b = 0; b < B; ++b)
             if (!x.branch_used[(size_t)b]) q.klen[(size_t)b] = 0;
-    uint32_t kmax = 0;
-    for (uint32_t k : q.klen) kmax = std::max(kmax, k);
     auto digits_of = [](uint32_t k) {
         int d = 1;
         while (d < 5 && (k >> (7 * d)) != 0) ++d;
         return d;
     };
+    auto pieces_of = [](uint32_t k) { return std::max<int64_t>(1, ((int64_t)k + TRI_KMAX - 1) / TRI_KMAX); };
+    const bool may_grade = env_int("FF_MFMA_GRADED", 1) != 0;
+    // Sparse tables: the rows few samples reach leave the matrix cores' operands (ff_kernels_low_unw.hpp).
+    // The matrix-core kernel multiplies every staged row against every pair of the shard, plane by plane: a row costs
+    // pairs x planes / M_PLANE_RATE whatever it holds (two planes up to two base-128 digits; graded beyond, three above
+    // DUO_KMAX, and a branch longer than TRI_KMAX as several rows), on top of M_PAIR_COST per pair whatever the rows.
+    // A rare row r with n_r flat nodes costs pair_low_unw_kernel n_r^2 / 2 LDS adds whatever the number of pairs and
+    // whatever its length, at LOW_UNW_ADD each, and LOW_UNW_VISIT for every block of pairs in which both sample blocks
+    // hold it (the look-up of its two lists and its length, the lanes' search, the first loads: latency, and most of
+    // the kernel's time where the lists are a few entries long) -- times the idle share of the blocks' last round on two
+    // workgroups per CU, which picks the block side.  A row is rare when that is cheaper than its matrix row(s), up to
+    // N / LOW_SHARE_DIV samples, and the split is taken when the whole estimate saves 7 % or more.  FF_UNW_SPLIT = 1 / 0
+    // forces (every row up to that cap) / forbids it; unset, it is considered only where the shard has a round of
+    // 256 x 128 tiles, so that pair_common_mfma_kernel is the plan's kernel (a shard below that may take
+    // pair_common_small_kernel, which does not know the rare rows' term).
+    //   Measured at 8,192 samples on a 50,000-leaf tree (profiles/r06_unw_split.txt): every row on the matrix cores,
+    //   99,999 rows of two planes over 3.36e7 pairs, 3.10 ms a pass, and 0.34 / 0.75 ms with 3,279 / 16,026 rows left:
+    //   28.6 ns a row -- 2.35e15 (pair, row, plane) per second -- and 0.24 ms whatever the rows, 7e-12 s a pair.  (The
+    //   first guess, 1.4e15 from profiles/r05_c3_unweighted_kernel_stats.csv at C3's 4,096 samples, was low.)
+    //   pair_low_unw_kernel, rows of up to 480 samples rare: 1.29 ms at 0.2 % leaf density (3.1e8 adds, 4.6e7 visits),
+    //   3.86 ms at 1 % (1.15e9 adds, 1.17e8 visits): 1.33e-12 s an add -- 7.5e11 per second, a third of the 2.4e12 that
+    //   pair_low_kernel reaches on the weighted plans' far longer lists -- and 1.37e-11 s a visit.
+    std::vector<int32_t> mat;  // the matrix rows' branches, in staged order
+    std::vector<int32_t> h_low;  // branch id -> rare row (-1: not one); empty: no split
+    int64_t Rl = 0;
+    {
+        const int force = env_int("FF_UNW_SPLIT", -1);
+        const bool big_kernel = env_int("FF_MFMA_SMALL", -1) <= 0 &&
+                                mfma_big_tiles(N, inf.row_begin, inf.row_end) >= (int64_t)inf.n_compute_units * M_WGS_PER_CU;
+        if (force != 0 && (force > 0 || big_kernel) && N >= 2 * LOW_TILE_MAX && nnz > 0 && R > 32) {
+            Scratch<int32_t> cnt;
+            FF_HIP(cnt.alloc((size_t)R));
+            FF_HIP(hipMemset(cnt.p, 0, sizeof(int32_t) * (size_t)R));
+            row_counts_kernel<<<dim3((unsigned)std::min<int64_t>((nnz + 255) / 256, 1 << 16)), dim3(256)>>>(d_ids, nnz, row_of.p, cnt.p);
+            FF_HIP(hipGetLastError());
+            std::vector<int32_t> h_cnt((size_t)R);
+            FF_HIP(hipMemcpy(h_cnt.data(), cnt.p, sizeof(int32_t) * (size_t)R, hipMemcpyDeviceToHost));
+            constexpr double M_PLANE_RATE = 2.35e15, M_PAIR_COST = 7e-12, LOW_UNW_ADD = 1.33e-12, LOW_UNW_VISIT = 1.37e-11;
+            const double Ps = std::max(1.0, (double)n_slots);  // (priced for THIS plan's shard, as stage_for_sad does)
+            uint32_t kmax_all = 0;
+            for (int64_t r = 0; r < R; ++r) kmax_all = std::max(kmax_all, q.klen[(size_t)(branch_of_row.empty() ? r : branch_of_row[(size_t)r])]);
+            const int d_all = digits_of(kmax_all);
+            const bool long_rows = d_all > 2 && may_grade;
+            auto t_matrix = [&](uint32_t k) {  // one branch in the matrix
+                const double planes = !long_rows ? (double)(std::min(d_all, 2) * ((d_all + 1) / 2))
+                                                 : (double)pieces_of(k) * (k > (uint32_t)DUO_KMAX ? 3.0 : 2.0);
+                return Ps * planes / M_PLANE_RATE;
+            };
+            // the block side: the one whose blocks of pairs fill their rounds best (ties: the larger)
+            const int forced_tile = env_int("FF_LOW_TILE", 0);
+            const double slots = 2.0 * (double)std::max(1, prop.multiProcessorCount);
+            int tile = 0;
+            double fill = 0, blocks = 1;
+            for (int cand : LOW_TILES) {
+                bool known = false;
+                for (int t : LOW_TILES) known = known || t == forced_tile;
+                if (known && cand != forced_tile) continue;
+                double tc = 0;  // the shard's blocks: sample blocks bi that hold one of its rows, times bj <= bi
+                for (int64_t bi = inf.row_begin / cand; bi * cand < std::min<int64_t>(inf.row_end, N); ++bi) tc += (double)(bi + 1);
+                tc = std::max(tc, 1.0);
+                const double f = std::ceil(tc / slots) * slots / tc;
+                if (tile == 0 || f < fill) {
+                    tile = cand;
+                    fill = f;
+                    blocks = tc;
+                }
+            }
+            // (the shard's share of a row's updates: its pairs of all)
+            const double share = Ps / std::max(1.0, 0.5 * (double)N * (double)(N - 1));
+            const int64_t cap = N / LOW_SHARE_DIV;
+            const double nblk = (double)((N + tile - 1) / tile);
+            double t_now = Ps * M_PAIR_COST, t_split = Ps * M_PAIR_COST, rare_entries = 0, upd = 0;
+            std::vector<int64_t> rare;
+            for (int64_t r = 0; r < R; ++r) {
+                const int64_t n = h_cnt[(size_t)r];
+                const double tm = t_matrix(q.klen[(size_t)(branch_of_row.empty() ? r : branch_of_row[(size_t)r])]);
+                const double in_block = 1.0 - std::exp(-(double)n / nblk);  // P(a sample block holds the row)
+                const double tl = (0.5 * (double)n * (double)n * share * LOW_UNW_ADD + blocks * in_block * in_block * LOW_UNW_VISIT) * fill;
+                t_now += tm;
+                if (n <= cap && (force > 0 || tl < tm)) {
+                    rare.push_back(r);
+                    t_split += tl;
+                    rare_entries += (double)n;
+                    upd += 0.5 * (double)n * (double)(n - 1);
+                } else {
+                    t_split += tm;
+                }
+            }
+            // (the index is (rare rows + 1) x sample blocks words, twice while it is built: not beyond 4 GB; and it counts
+            // the rare rows' entries in 32 bits)
+            const bool fits = 8.0 * (double)(rare.size() + 1) * (double)((N + tile - 1) / tile) <= 4e9 && rare_entries < 4.0e9;
+            if (!rare.empty() && fits && (force > 0 || t_split <= 0.93 * t_now)) {
+                // numbered by DESCENDING sample count, as the weighted rare rows are: the 64 rows of a bitmap word are
+                // worked together by a wave, and rows of like weight side by side keep its rounds' lists alike
+                std::stable_sort(rare.begin(), rare.end(), [&](int64_t u, int64_t v) { return h_cnt[(size_t)u] > h_cnt[(size_t)v]; });
+                h_low.assign((size_t)B, -1);
+                for (int64_t r : rare) h_low[(size_t)(branch_of_row.empty() ? r : branch_of_row[(size_t)r])] = (int32_t)Rl++;
+                pl->split = true;
+                pl->low_tile = tile;
+                pl->low_rows = Rl;
+                inf.rare_rows = Rl;
+                inf.rare_updates = upd * share;  // (LDS adds: the kernel's own work)
+            }
+        }
+    }
+    for (int64_t r = 0; r < R; ++r) {
+        const int32_t b = (int32_t)(branch_of_row.empty() ? r : branch_of_row[(size_t)r]);
+        if (h_low.empty() || h_low[(size_t)b] < 0) mat.push_back(b);
+    }
+    const int64_t Rm = (int64_t)mat.size();
+    uint32_t kmax = 0;  // (over the matrix rows: a long rare branch does not decide the sweep's digits)
+    if (!pl->split) for (uint32_t k : q.klen) kmax = std::max(kmax, k);
+    else for (const int32_t b : mat) kmax = std::max(kmax, q.klen[(size_t)b]);
     int digits = digits_of(kmax);
     // The staged rows: (branch, integer length of the row).  Up to two base-128 digits -- short binary fractions,
     // C3's generator -- a row is a branch in use, in ascending order, and a sweep multiplies both digit planes.
@@ -446,20 +609,16 @@ int stage_for_mfma(StageCtx &x, char *err, size_t errlen)
     };
     std::vector<StagedRow> rows;
     bool graded = false;
-    if (digits > 2 && env_int("FF_MFMA_GRADED", 1) != 0) {
+    if (digits > 2 && may_grade) {
         int64_t pieces = 0;
-        for (int64_t r = 0; r < R; ++r) {
-            const int64_t k = q.klen[(size_t)(branch_of_row.empty() ? r : branch_of_row[(size_t)r])];
-            pieces += std::max<int64_t>(1, (k + TRI_KMAX - 1) / TRI_KMAX);
-        }
+        for (const int32_t b : mat) pieces += pieces_of(q.klen[(size_t)b]);
         // (a few long branches, not a tree of them: three planes over x times the rows against two sweeps of two
         // planes, or three sweeps from five base-128 digits)
-        if (pieces <= (digits < 5 ? R + R / 4 : R + R * 4 / 5) + 1024 && pieces < ((int64_t)1 << 30)) {
+        if (pieces <= (digits < 5 ? Rm + Rm / 4 : Rm + Rm * 4 / 5) + 1024 && pieces < ((int64_t)1 << 30)) {
             graded = true;
             rows.reserve((size_t)pieces);
-            for (int64_t r = 0; r < R; ++r) {
-                const int32_t b = (int32_t)(branch_of_row.empty() ? r : branch_of_row[(size_t)r]);
-                const int64_t k = q.klen[(size_t)b], n = std::max<int64_t>(1, (k + TRI_KMAX - 1) / TRI_KMAX);
+            for (const int32_t b : mat) {
+                const int64_t k = q.klen[(size_t)b], n = pieces_of((uint32_t)k);
                 for (int64_t j = 0; j < n; ++j) rows.push_back({b, (uint32_t)(k / n + (j < k % n ? 1 : 0))});
             }
             std::stable_sort(rows.begin(), rows.end(), [](const StagedRow &u, const StagedRow &v) { return u.k > v.k; });
@@ -467,11 +626,8 @@ int stage_for_mfma(StageCtx &x, char *err, size_t errlen)
         }
     }
     if (!graded) {
-        rows.reserve((size_t)R);
-        for (int64_t r = 0; r < R; ++r) {
-            const int32_t b = (int32_t)(branch_of_row.empty() ? r : branch_of_row[(size_t)r]);
-            rows.push_back({b, q.klen[(size_t)b]});
-        }
+        rows.reserve((size_t)Rm);
+        for (const int32_t b : mat) rows.push_back({b, q.klen[(size_t)b]});
     }
     const int64_t Rs = (int64_t)rows.size();  // staged rows
     pl->m_digits = digits;
@@ -528,10 +684,11 @@ int stage_for_mfma(StageCtx &x, char *err, size_t errlen)
         }
     }
     Scratch<uint32_t> klen;
-    Scratch<int32_t> row_ptr, row_list;  // graded: the rows of a branch (it may have several)
+    Scratch<int32_t> row_ptr, row_list;  // graded: the rows of a branch (it may have several); split: a rare branch has none
     FF_HIP(klen.alloc((size_t)B));
     FF_HIP(hipMemcpy(klen.p, q.klen.data(), sizeof(uint32_t) * (size_t)B, hipMemcpyHostToDevice));
-    if (graded) {
+    const bool by_lists = graded || pl->split;
+    if (by_lists) {
         std::vector<int32_t> ptr((size_t)B + 1, 0), list((size_t)std::max<int64_t>(Rs, 1));
         for (const StagedRow &sr : rows) ++ptr[(size_t)sr.branch + 1];
         for (int64_t b = 0; b < B; ++b) ptr[(size_t)b + 1] += ptr[(size_t)b];
@@ -543,11 +700,26 @@ int stage_for_mfma(StageCtx &x, char *err, size_t errlen)
         FF_HIP(hipMemcpy(row_list.p, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice));
     }
     if (nnz > 0)
-        stage_mfma_bits_kernel<<<dim3((unsigned)N), dim3(256)>>>(d_indptr, d_ids, klen.p, graded ? nullptr : row_of.p,
+        stage_mfma_bits_kernel<<<dim3((unsigned)N), dim3(256)>>>(d_indptr, d_ids, klen.p, by_lists ? nullptr : row_of.p,
                                                                   row_ptr.p, row_list.p, pl->d_Pbits, n8, n_slabs, pl->d_W);
     FF_HIP(hipGetLastError());
     FF_HIP(hipDeviceSynchronize());
     klen.release();
+    if (pl->split) {
+        // the rare rows: W above holds their lengths (every flat node's), the presence bits do not; their entries by
+        // sample block, and k by rare row -- whole, whatever its digits
+        Scratch<int32_t> low_of;
+        FF_HIP(low_of.alloc((size_t)B));
+        FF_HIP(hipMemcpy(low_of.p, h_low.data(), sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice));
+        const int rc = build_low_index(x, low_of.p, Rl, q.e, err, errlen);
+        if (rc != FF_OK) return rc;
+        std::vector<uint32_t> k_low((size_t)Rl);
+        for (int64_t b = 0; b < B; ++b)
+            if (h_low[(size_t)b] >= 0) k_low[(size_t)h_low[(size_t)b]] = q.klen[(size_t)b];
+        FF_HIP(hipMalloc(&pl->d_low_k, sizeof(uint32_t) * (size_t)Rl));
+        FF_HIP(hipMemcpy(pl->d_low_k, k_low.data(), sizeof(uint32_t) * (size_t)Rl, hipMemcpyHostToDevice));
+        inf.staged_bytes += 4.0 * (double)Rl;
+    }
     return schedule_mfma(pl, err, errlen);
 }
 
@@ -699,7 +871,6 @@ int stage_for_sad(StageCtx &x, char *err, size_t errlen)
         if (B > 0) FF_HIP(hipMemcpy(klen.p, q.klen.data(), sizeof(uint32_t) * (size_t)B, hipMemcpyHostToDevice));
     }
     std::vector<unsigned long long> hW((size_t)ld);
-    const int nb = pl->split ? (int)((N + pl->low_tile - 1) / pl->low_tile) : 0;
     if (pl->split) {
         FF_HIP(hipMalloc(&pl->d_Wl, sizeof(uint32_t) * (size_t)ld));
         FF_HIP(hipMemset(pl->d_Wl, 0, sizeof(uint32_t) * (size_t)ld));
@@ -731,43 +902,8 @@ int stage_for_sad(StageCtx &x, char *err, size_t errlen)
     klen.release();
     inf.scale_log2 = e;
     if (pl->split) {
-        // the rare rows' entries grouped by sample block: counts -> positions -> (sample, value) pairs -> row bitmaps
-        pl->low_blocks = nb;
-        pl->low_words = (Rl + 63) / 64;
-        const int64_t rows1 = Rl + 1;
-        const size_t cells = (size_t)rows1 * (size_t)nb;
-        FF_ALLOC(pl->d_low_ptr, sizeof(uint32_t) * cells, "the rare rows' index");
-        FF_HIP(hipMemset(pl->d_low_ptr, 0, sizeof(uint32_t) * cells));
-        low_sums_counts_kernel<<<dim3((unsigned)N), dim3(256)>>>(d_indptr, d_ids, d_abnd, d_len, e, low_of.p, rows1, pl->low_tile, pl->d_low_ptr,
-                                                                  nullptr, nullptr);
-        Scratch<uint32_t> totals, cursor;
-        FF_HIP(totals.alloc((size_t)nb + 1));
-        FF_HIP(cursor.alloc(cells));
-        FF_HIP(hipMemset(cursor.p, 0, sizeof(uint32_t) * cells));
-        // per block: exclusive prefix over its rows1 positions (the last one becomes the block's total), then the
-        // blocks' bases
-        scan_segments_kernel<<<dim3((unsigned)nb), dim3(1024)>>>(pl->d_low_ptr, rows1, rows1, totals.p);
-        FF_HIP(hipGetLastError());
-        std::vector<uint32_t> h_tot((size_t)nb), h_base((size_t)nb + 1, 0u);
-        FF_HIP(hipMemcpy(h_tot.data(), totals.p, sizeof(uint32_t) * (size_t)nb, hipMemcpyDeviceToHost));
-        uint64_t run = 0;
-        for (int k = 0; k < nb; ++k) {
-            h_base[(size_t)k] = (uint32_t)run;
-            run += h_tot[(size_t)k];
-        }
-        if (run >= 0xFFFFFFF0ull) return ff::fail(FF_ERR_INTERNAL, err, errlen, "too many rare-row entries");
-        const uint32_t n_entries = (uint32_t)run;
-        FF_HIP(hipMemcpy(totals.p, h_base.data(), sizeof(uint32_t) * (size_t)nb, hipMemcpyHostToDevice));
-        low_add_base_kernel<<<dim3((unsigned)((cells + 255) / 256)), dim3(256)>>>(pl->d_low_ptr, rows1, nb, totals.p);
-        FF_ALLOC(pl->d_low_ent, sizeof(uint2) * ((size_t)n_entries + 4), "the rare rows' entries");
-        FF_HIP(hipMemset(pl->d_low_ent + n_entries, 0, sizeof(uint2) * 4));  // (spare: pair_low_kernel loads four at a time, and adds the zeros)
-        low_fill_kernel<<<dim3((unsigned)N), dim3(256)>>>(d_indptr, d_ids, d_abnd, d_len, e, low_of.p, rows1, pl->low_tile, pl->d_low_ptr, cursor.p,
-                                                           pl->d_low_ent);
-        FF_ALLOC(pl->d_low_bits, sizeof(unsigned long long) * (size_t)nb * (size_t)pl->low_words, "the rare rows' bitmaps");
-        low_bits_kernel<<<dim3((unsigned)pl->low_words, (unsigned)nb), dim3(64)>>>(pl->d_low_ptr, Rl, rows1, pl->low_words, pl->d_low_bits);
-        FF_HIP(hipGetLastError());
-        FF_HIP(hipDeviceSynchronize());  // (the scratch arrays go out of scope)
-        inf.staged_bytes += 4.0 * (double)cells + 8.0 * (double)n_entries + 8.0 * (double)nb * (double)pl->low_words;
+        const int rc = build_low_index(x, low_of.p, Rl, e, err, errlen);
+        if (rc != FF_OK) return rc;
     }
     pl->n_workgroups = prop.multiProcessorCount;  // persistent: one workgroup per CU
     pl->lds_bytes = 96 * 1024;  // unused dynamic LDS sized so that exactly one workgroup fits a CU

@@ -97,6 +97,8 @@ void plan_free_device(ff_plan *pl)
     (void)hipFree(pl->d_cs16);
     (void)hipFree(pl->d_low_ptr);
     (void)hipFree(pl->d_low_ent);
+    (void)hipFree(pl->d_low_ent16);
+    (void)hipFree(pl->d_low_k);
     (void)hipFree(pl->d_low_bits);
     (void)hipFree(pl->d_Wl);
     (void)hipFree(pl->d_mlow);
@@ -389,7 +391,10 @@ int ff_plan_timing_collect_parts(ff_plan *pl, double *total_ms, double *rare_ms,
         if (hipEventSynchronize(pl->events[k].second) != hipSuccess ||
             hipEventElapsedTime(&ms, pl->events[k].first, pl->events[k].second) != hipSuccess)
             return FF_ERR_DEVICE;
-        if (parts && hipEventElapsedTime(&low, pl->events[k].mid, pl->events[k].second) != hipSuccess) return FF_ERR_DEVICE;
+        // (the rare rows' kernel runs behind the matrix rows' in a weighted plan, ahead of them in an unweighted one)
+        if (parts && hipEventElapsedTime(&low, pl->mfma ? pl->events[k].first : pl->events[k].mid,
+                                         pl->mfma ? pl->events[k].mid : pl->events[k].second) != hipSuccess)
+            return FF_ERR_DEVICE;
         sum += (double)ms;
         rare += (double)low;
         ++n;

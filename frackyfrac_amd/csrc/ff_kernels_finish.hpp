@@ -36,7 +36,7 @@ void finish_fixed32_kernel(const uint32_t *__restrict__ num,
         }
 #pragma unroll
         for (int e = 0; e < FINISH_RUN; ++e, t += 256) {
-            if (t < n_slots) finish_pair(f, t, i, j, f.mlow ? u32[e] + f.wl[i] + f.wl[j] : u32[e], h2min);
+            if (t < n_slots) finish_pair_w(f, t, i, j, f.wl ? u32[e] + f.wl[i] + f.wl[j] : u32[e], f.W[i] + f.W[j], h2min);
             j += 256;
             while (j >= i) {  // (rows are shorter than 256 only at the top of the triangle)
                 j -= i;

@@ -38,7 +38,8 @@ struct FinishArgs {
     unsigned long long refine_cap;
     unsigned long long *risk_list;  // local slots of the pairs just above the refinement rule's bound (null: none kept)
     int scale_log2, weighted;
-    // sparse tables (ff_kernels_low.hpp): the numerator is num + wl[i] + wl[j] - 2 mlow[t]; null: num alone
+    // sparse tables (ff_kernels_low.hpp): the numerator is num + wl[i] + wl[j] - 2 mlow[t]; null: num alone.
+    // Unweighted (ff_kernels_low_unw.hpp): num - 2 mlow[t], wl null -- W and so num hold the rare rows' lengths already.
     const uint32_t *mlow, *wl;
 };
 
@@ -84,9 +85,14 @@ __device__ __forceinline__ void finish_pair_w(const FinishArgs &f, int64_t t, in
     }
 }
 
-// Local slot t = pair (i, j), integer numerator u.
-__device__ __forceinline__ void finish_pair(const FinishArgs &f, int64_t t, int64_t i, int64_t j, unsigned long long u, float &h2min)
+// Local slot t = pair (i, j), integer numerator u modulo 2^32 as the matrix-core path's kernels hold it: W_i + W_j - 2
+// common over the MATRIX rows.  Every exit of that path that writes a distance comes through here (the in-place finish
+// of pair_common_mfma_kernel, reduce_private_kernel, reduce_partials_kernel), so this is where a split plan's rare rows
+// come off: U = u - 2 mlow[t] (ff_kernels_low_unw.hpp; W holds every row, so there is no wl).  The exits that leave sums
+// in num[] go through finish_fixed32_kernel, which subtracts the term itself.
+__device__ __forceinline__ void finish_pair(const FinishArgs &f, int64_t t, int64_t i, int64_t j, uint32_t u, float &h2min)
 {
+    if (f.mlow) u -= 2u * f.mlow[t];
     finish_pair_w(f, t, i, j, u, f.W[i] + f.W[j], h2min);
 }
 

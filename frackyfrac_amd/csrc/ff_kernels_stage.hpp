@@ -315,6 +315,22 @@ void low_fill_kernel(const int64_t *__restrict__ indptr, const int32_t *__restri
     }
 }
 
+// The same for an unweighted plan (pair_low_unw_kernel): an entry is the byte offset of its sample's accumulator row
+// alone, 16 bits; the row's integer length is kept by rare row, not by entry.
+__global__ __launch_bounds__(256)
+void low_fill_unw_kernel(const int64_t *__restrict__ indptr, const int32_t *__restrict__ branch_id,
+                         const int32_t *__restrict__ low_of, int64_t rows1, int tile, const uint32_t *__restrict__ ptr,
+                         uint32_t *__restrict__ cursor, uint16_t *__restrict__ entries)
+{
+    const int64_t s = blockIdx.x;
+    for (int64_t t = indptr[s] + threadIdx.x; t < indptr[s + 1]; t += blockDim.x) {
+        const int32_t r = low_of[branch_id[t]];
+        if (r < 0) continue;
+        const int64_t cell = (s / tile) * rows1 + r;
+        entries[ptr[cell] + atomicAdd(&cursor[cell], 1u)] = (uint16_t)((uint32_t)(s % tile) << LOW_ROW_SHIFT);
+    }
+}
+
 // bits[block][w] bit t: rare row 64 w + t has an entry in the sample block.  One wave per (word, block).
 __global__ void low_bits_kernel(const uint32_t *__restrict__ ptr, int64_t n_rows, int64_t rows1, int64_t words,
                                 unsigned long long *__restrict__ bits)

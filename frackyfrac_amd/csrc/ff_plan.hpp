@@ -59,9 +59,11 @@ struct ff_plan {
     int64_t low_words = 0;                // 64-bit words of a block's row bitmap
     uint32_t *d_low_ptr = nullptr;        // [low_blocks][low_rows + 1]: where row r's entries of block k begin
     uint2 *d_low_ent = nullptr;           // entries: (sample's index within its block, staged value)
+    uint16_t *d_low_ent16 = nullptr;      // unweighted (pair_low_unw_kernel): the sample's place within its block alone
+    uint32_t *d_low_k = nullptr;          //   and the integer length by rare row
     unsigned long long *d_low_bits = nullptr;  // [low_blocks][low_words]: rows with an entry in the block
     uint32_t *d_Wl = nullptr;             // [ld] column sums over the rare rows
-    uint32_t *d_mlow = nullptr;           // [slots of the shard] sum over the rare rows of min(q_i, q_j)
+    uint32_t *d_mlow = nullptr;           // [slots of the shard] sum over the rare rows of min(q_i, q_j); unweighted: of k_r where both have it
     ff::sched::LowTile *d_low_tiles = nullptr;
     int n_low_tiles = 0;
     // refinement of nearly-equal pairs: the flat nodes stay on the device
@@ -116,7 +118,8 @@ struct ff_plan {
     ff::sched::XUTile *d_xutiles = nullptr;
     int n_xutiles = 0;
     // timing: the events of every timed run since the last collect -- around the pair reduction, and between the matrix
-    // rows' kernel and the rare rows' (recorded only where the plan is split: `split` says which)
+    // rows' kernel and the rare rows' (recorded only where the plan is split: `split` says which; the rare rows' kernel
+    // runs second in a weighted plan, first in an unweighted one)
     struct TimedRun { hipEvent_t first, second, mid; };
     std::vector<TimedRun> events;
     size_t events_used = 0;

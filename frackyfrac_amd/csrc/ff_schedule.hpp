@@ -67,6 +67,13 @@ constexpr int LOW_COL_SHIFT = 7;    // li * LOW_STRIDE * 4 -> li * 4
 struct LowTile {
     int32_t bi, bj;  // sample blocks: pairs (i, j) with i in block bi, j in block bj <= bi, j < i
 };
+// pair_low_unw_kernel (unweighted: an entry is that byte offset alone, 16 bits) walks a row's A entries one 16-byte load
+// -- LOW_UNW_LOAD entries -- at a time from wherever the list begins: the load of a list's last step reads up to
+// LOW_UNW_LOAD - 1 entries past the list's, and so the array's, end.  The spare entries behind the array are zeros.
+constexpr int LOW_UNW_LOAD = 8;
+constexpr int LOW_UNW_SPARE = 8;
+static_assert(LOW_UNW_LOAD * 2 == 16 && LOW_UNW_SPARE >= LOW_UNW_LOAD - 1, "the rare rows' spare entries must cover pair_low_unw_kernel's last load");
+inline int64_t low_unw_alloc_entries(int64_t n_entries) { return n_entries + LOW_UNW_SPARE; }
 
 struct Item {        // one unit of work for a persistent wave: a pair tile over a
     int32_t i0, j0;  // branch range [k0, k1)
@@ -122,6 +129,14 @@ constexpr int M_PAD_SLABS = 12; // slabs of zero padding behind the presence wor
 static_assert(M_PAD_SLABS >= M_SLABS_AHEAD && M_PAD_SLABS % 2 == 0, "the prefetch of pair_common_mfma_kernel must stay inside the padding");
 inline int64_t mfma_staged_slabs(int64_t R) { return round_up(R > 0 ? R : 1, (int64_t)M_KSLAB * M_QUAD_SLABS) / M_KSLAB; }
 inline int64_t mfma_alloc_slabs(int64_t R) { return mfma_staged_slabs(R) + M_PAD_SLABS; }
+// the 256 x 128 tiles of a shard's rows [rb, re): fewer than workgroups, and the shard may take pair_common_small_kernel
+inline int64_t mfma_big_tiles(int64_t N, int64_t rb, int64_t re)
+{
+    int64_t n = 0;
+    for (int64_t i0 = rb / M_TILE_I * M_TILE_I; i0 < re; i0 += M_TILE_I)
+        n += (std::min<int64_t>(std::min<int64_t>(i0 + M_TILE_I, re) - 1, N) + M_TILE_J - 1) / M_TILE_J;
+    return n;
+}
 constexpr int M_ND = 2;        // digit planes multiplied per sweep of the presence operand
 // pair_common_mfma_kernel<.., GRADED>: three SIGNED digit planes in one sweep, k = d0 + 128 d1 + 32768 d2 with
 // d0 in [-64, 63], d1 in [-127, 128], d2 in [0, 127]; where every d2 is zero the sweep multiplies two planes.

@@ -82,7 +82,10 @@ typedef enum ff_precision {
                                  binary64 denominators, exact re-computation of near-equal
                                  pairs, run-time audit);
                                  weighted runs on the vector ALU (v_sad_u32), unweighted on
-                                 the int8 matrix cores (same integers, same results)          */
+                                 the int8 matrix cores (same integers, same results); on a
+                                 sparse table the rows few samples reach leave the matrix of
+                                 either and are reduced over the pairs that both have them
+                                 (ff_plan_info.rare_rows; same integers again)                */
     FF_PRECISION_EXACT64 = 2  /* binary64 in the reference's own summation order: bit-for-bit
                                  the reference for every input it accepts (negative, infinite
                                  and NaN branch lengths included: a tree with a non-finite
@@ -223,10 +226,13 @@ typedef struct ff_plan_info {
     double active_fraction;    /* FIXED32 weighted: share of the shard's (32-sample block, staged row) cells in
                                   which some sample has the branch -- what pair_sad_sparse_kernel walks (it skips
                                   the rest) and what decides between it and the dense kernel; 1 where not counted */
-    int64_t rare_rows;         /* FIXED32 weighted on a sparse table: staged rows kept OUT of the matrix (few samples
-                                  reach them) and reduced by pair_low_kernel over the pairs that both have them; 0: none */
-    double rare_updates;       /* pair_low_kernel's own work per pass: the sum over the rare rows of n_r (n_r - 1) / 2, n_r =
-                                  the samples with a flat node on the row (an update = one min + one LDS add).
+    int64_t rare_rows;         /* FIXED32 on a sparse table: staged rows kept OUT of the matrix (few samples reach
+                                  them) and reduced over the pairs that both have them -- by pair_low_kernel
+                                  (weighted), by pair_low_unw_kernel ahead of the matrix cores (unweighted: `kernel`
+                                  stays FF_KERNEL_MFMA_I8); 0: none */
+    double rare_updates;       /* that kernel's own work per pass: the sum over the rare rows of n_r (n_r - 1) / 2, n_r =
+                                  the samples with a flat node on the row (weighted: an update = one min + one LDS add,
+                                  DESIGN 4.2; unweighted: one LDS add of the row's integer length).
                                   A row shard's plan: the whole triangle's count times the shard's share of the pairs */
 } ff_plan_info;
 
@@ -293,7 +299,7 @@ int ff_plan_run_host(ff_plan *plan, double *out, char *err, size_t errlen);
  */
 int ff_plan_run_timed(ff_plan *plan, void *stream, double *d_out, char *err, size_t errlen);
 int ff_plan_timing_collect(ff_plan *plan, double *total_ms, int32_t *launches);
-/* The same with the share of the rare rows' kernel (pair_low_kernel, ff_plan_info.rare_rows > 0: the rest of total_ms is
+/* The same with the share of the rare rows' kernel (pair_low_kernel / pair_low_unw_kernel, ff_plan_info.rare_rows > 0: the rest of total_ms is
  * the matrix rows' kernel; 0 where the plan is not split) -- so that a benchmark can price each kernel on its own rows. */
 int ff_plan_timing_collect_parts(ff_plan *plan, double *total_ms, double *rare_ms, int32_t *launches);
 
