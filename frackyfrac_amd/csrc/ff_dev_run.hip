@@ -306,7 +306,12 @@ int launch_exact64(ff_plan *pl, hipStream_t st, double *d_out, char *err, size_t
 {
     const ff_plan_info &inf = pl->info;
     if (pl->xu) {
-        if (pl->n_xutiles > 0)
+        if (pl->n_xutiles > 0 && pl->xu_skip)
+            pair_exact_unw_skip_kernel<<<dim3((unsigned)pl->n_xutiles), dim3(64), 0, st>>>(pl->d_Xbits, pl->xu_ldx, pl->d_xu_len_words,
+                                                                                          (pl->xu_slabs + XU_OCC_LOAD - 1) / XU_OCC_LOAD, pl->d_xu_rowocc,
+                                                                                          pl->d_xu_colocc, pl->xu_occ_stride, pl->d_xutiles,
+                                                                                          inf.row_begin, inf.row_end, inf.slot_begin, d_out);
+        else if (pl->n_xutiles > 0)
             pair_exact_unw_kernel<<<dim3((unsigned)pl->n_xutiles), dim3(64), 0, st>>>(pl->d_Xbits, pl->xu_ldx, pl->d_len_rows, pl->xu_slabs,
                                                                                      pl->d_xutiles, inf.row_begin, inf.row_end,
                                                                                      inf.slot_begin, d_out);
@@ -413,6 +418,32 @@ int schedule_exact_unw(ff_plan *pl, char *err, size_t errlen)
     pl->n_xutiles = (int)tiles.size();
     FF_HIP(hipMalloc(&pl->d_xutiles, sizeof(XUTile) * std::max<size_t>(tiles.size(), 1)));
     if (!tiles.empty()) FF_HIP(hipMemcpy(pl->d_xutiles, tiles.data(), sizeof(XUTile) * tiles.size(), hipMemcpyHostToDevice));
+    // The row-skipping form (pair_exact_unw_skip_kernel) on the same tiles: what it would visit is counted exactly, on
+    // the device, and the two forms' times are estimated from the counts (DESIGN 4.11 has the constants' measurement):
+    // the dense form pays per (tile, row), the skipping one per visited (tile, row) and per (tile, slab) that is not
+    // empty.  Taken when estimated 7 % or more under the dense form; FF_XU_SKIP=1 forces it, 0 (no occupancy words
+    // were staged) forbids it.
+    pl->xu_skip = false;
+    inf.active_fraction = 1.0;
+    if (!pl->d_xu_rowocc || tiles.empty()) return FF_OK;
+    Scratch<unsigned long long> counts;
+    FF_HIP(counts.alloc(XU_CNT_N));
+    FF_HIP(hipMemset(counts.p, 0, sizeof(unsigned long long) * XU_CNT_N));
+    xu_visit_count_kernel<<<dim3((unsigned)tiles.size()), dim3(64)>>>(pl->d_xutiles, pl->d_xu_rowocc, pl->d_xu_colocc, pl->xu_occ_stride,
+                                                                      pl->xu_slabs, counts.p);
+    FF_HIP(hipGetLastError());
+    unsigned long long cnt[XU_CNT_N];
+    FF_HIP(hipMemcpy(cnt, counts.p, sizeof(cnt), hipMemcpyDeviceToHost));
+    const double cells = (double)tiles.size() * (double)inf.n_rows;
+    const double t_dense = XU_NS_DENSE_ROW * cells;
+    const double t_skip = XU_NS_SKIP_ROW * (double)cnt[XU_CNT_ROWS] + XU_NS_SKIP_SLAB * (double)cnt[XU_CNT_SLABS];
+    const int want = env_int("FF_XU_SKIP", -1);
+    pl->xu_skip = want == 1 || (want != 0 && t_skip < 0.93 * t_dense);
+    if (pl->xu_skip) {
+        inf.active_fraction = cells > 0 ? (double)cnt[XU_CNT_ROWS] / cells : 0.0;
+        inf.n_items = (int64_t)cnt[XU_CNT_SLABS];  // the (tile, slab) cells the walk stops at
+        inf.elements = 64.0 * XU_TILE_H * (double)cnt[XU_CNT_ROWS_J];
+    }
     return FF_OK;
 }
 

@@ -988,10 +988,37 @@ int stage_for_exact_unw(StageCtx &x, char *err, size_t errlen)
     if (N > 0 && nnz > 0)
         stage_xbits_kernel<<<dim3((unsigned)N), dim3(256)>>>(d_indptr, d_ids, row_of.p, pl->d_Xbits, ldx);
     FF_HIP(hipGetLastError());
+    // The group-occupancy words of the row-skipping form (they do not depend on the shard; FF_XU_SKIP=0 needs none).
+    if (env_int("FF_XU_SKIP", 1) != 0) {
+        pl->xu_occ_stride = xu_occ_stride(R);
+        const size_t row_bytes = sizeof(uint32_t) * (size_t)xu_occ_row_groups(N) * (size_t)pl->xu_occ_stride;
+        const size_t col_bytes = sizeof(uint32_t) * (size_t)xu_occ_col_groups(N) * (size_t)pl->xu_occ_stride;
+        if (xu_occ_col_groups(N) > 65535) return ff::fail(FF_ERR_ARG, err, errlen, "EXACT64 unweighted: %lld samples, at most %d", (long long)N, 65535 * 64);
+        inf.staged_bytes += (double)row_bytes + (double)col_bytes;
+        FF_ALLOC(pl->d_xu_rowocc, row_bytes, "the row groups' occupancy words");
+        FF_ALLOC(pl->d_xu_colocc, col_bytes, "the column groups' occupancy words");
+        FF_HIP(hipMemset(pl->d_xu_rowocc, 0, row_bytes));
+        FF_HIP(hipMemset(pl->d_xu_colocc, 0, col_bytes));
+        xu_occupancy_kernel<<<dim3((unsigned)pl->xu_slabs, (unsigned)xu_occ_col_groups(N)), dim3(64)>>>(pl->d_Xbits, ldx, pl->xu_occ_stride,
+                                                                                                      pl->d_xu_rowocc, pl->d_xu_colocc);
+        FF_HIP(hipGetLastError());
+    }
     std::vector<double> lr(len_count, 0.0);  // treeDists by staged row, zeros behind
     for (int64_t r = 0; r < R; ++r) lr[(size_t)r] = c->h_len[(size_t)(branch_of_row.empty() ? r : branch_of_row[(size_t)r])];
     FF_HIP(hipMalloc(&pl->d_len_rows, sizeof(double) * len_count));
     FF_HIP(hipMemcpy(pl->d_len_rows, lr.data(), sizeof(double) * len_count, hipMemcpyHostToDevice));
+    if (pl->d_xu_rowocc) {  // the same lengths as the skipping form's lanes load them: a slab's 32 low words, then its 32 high words
+        std::vector<uint32_t> lw(2 * (size_t)xu_slabs(R) * XU_SLAB);
+        for (size_t r = 0; r < lw.size() / 2; ++r) {
+            uint64_t u;
+            memcpy(&u, &lr[r], 8);
+            lw[r / XU_SLAB * 2 * XU_SLAB + r % XU_SLAB] = (uint32_t)u;
+            lw[r / XU_SLAB * 2 * XU_SLAB + XU_SLAB + r % XU_SLAB] = (uint32_t)(u >> 32);
+        }
+        FF_HIP(hipMalloc(&pl->d_xu_len_words, sizeof(uint32_t) * lw.size()));
+        FF_HIP(hipMemcpy(pl->d_xu_len_words, lw.data(), sizeof(uint32_t) * lw.size(), hipMemcpyHostToDevice));
+        inf.staged_bytes += 4.0 * (double)lw.size();
+    }
     return schedule_exact_unw(pl, err, errlen);
 }
 

@@ -128,6 +128,9 @@ void plan_free_device(ff_plan *pl)
     (void)hipFree(pl->d_xtiles);
     (void)hipFree(pl->d_Xbits);
     (void)hipFree(pl->d_xutiles);
+    (void)hipFree(pl->d_xu_rowocc);
+    (void)hipFree(pl->d_xu_colocc);
+    (void)hipFree(pl->d_xu_len_words);
     for (auto &e : pl->events) {
         (void)hipEventDestroy(e.first);
         (void)hipEventDestroy(e.second);

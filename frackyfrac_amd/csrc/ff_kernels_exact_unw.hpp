@@ -76,6 +76,24 @@ static_assert(XU_TILE_H == 8, "pair_exact_unw_kernel: the asm block spells out e
 typedef const __attribute__((address_space(4))) uint32_t *xu_c32;  // (the constant address space: the compiler
 typedef const __attribute__((address_space(4))) uint64_t *xu_c64;  //  then fetches uniform addresses by scalar loads)
 
+// The distances of a tile's pairs from their two sums (shared by the dense and the skipping form).
+template <int J>
+__device__ __forceinline__ void xu_write_out(const double (&res)[XU_TILE_H][J], const double (&com)[XU_TILE_H][J], int i0, int j0,
+                                             int64_t row_begin, int64_t row_end, int64_t slot_begin, double *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int r = 0; r < XU_TILE_H; ++r) {
+        const int64_t i = (int64_t)i0 + r;
+        if (i < row_begin || i >= row_end) continue;
+#pragma unroll
+        for (int t = 0; t < J; ++t) {
+            const int64_t j = (int64_t)j0 + 64 * t + lane;
+            if (j < i) out[i * (i - 1) / 2 - slot_begin + j] = res[r][t] / (res[r][t] + com[r][t]);  // :169
+        }
+    }
+}
+
 template <int J>
 __device__ __forceinline__ void exact_unw_tile(const uint32_t *__restrict__ Xb, int64_t ldx,
                                                const double *__restrict__ len, int n_slabs, int i0, int j0,
@@ -134,16 +152,7 @@ __device__ __forceinline__ void exact_unw_tile(const uint32_t *__restrict__ Xb, 
         for (int r = 0; r < H; ++r) wi[r] = win[r];
     }
     static_assert(XU_SLAB % XU_LEN_STEP == 0, "exact_unw_tile: whole steps per slab");
-#pragma unroll
-    for (int r = 0; r < H; ++r) {
-        const int64_t i = (int64_t)i0 + r;
-        if (i < row_begin || i >= row_end) continue;
-#pragma unroll
-        for (int t = 0; t < J; ++t) {
-            const int64_t j = (int64_t)j0 + 64 * t + lane;
-            if (j < i) out[i * (i - 1) / 2 - slot_begin + j] = res[r][t] / (res[r][t] + com[r][t]);  // :169
-        }
-    }
+    xu_write_out<J>(res, com, i0, j0, row_begin, row_end, slot_begin, out);
 }
 
 // One wave per tile (64-thread workgroups: the hardware hands the next tile to whichever SIMD has room; the list is
@@ -159,4 +168,143 @@ void pair_exact_unw_kernel(const uint32_t *__restrict__ Xb, int64_t ldx, const d
     const int i0 = __builtin_amdgcn_readfirstlane(tile.i0), j0 = __builtin_amdgcn_readfirstlane(tile.j0);
     if (__builtin_amdgcn_readfirstlane(tile.jn) == 2) exact_unw_tile<2>(Xb, ldx, len, n_slabs, i0, j0, row_begin, row_end, slot_begin, out);
     else exact_unw_tile<1>(Xb, ldx, len, n_slabs, i0, j0, row_begin, row_end, slot_begin, out);
+}
+
+// ---- The row-skipping form: pair_exact_unw_skip_kernel ------------------------------------------------------------
+// The dense kernel runs a branch's block whether or not any of the tile's 8 + 64 J samples has the branch.  A branch
+// none of them has adds +0.0 to every chain of the tile and changes no accumulator: leaving it out gives the same bits,
+// and the branches that remain are still visited in ascending staged order.  On a sparse table most (tile, branch)
+// cells are of that kind (ff_plan_info.active_fraction).
+//
+//   * Which branches a tile touches comes from the group-occupancy words (xu_occupancy_kernel, ff_kernels_stage.hpp):
+//     per slab the OR of the presence words of the tile's row group and of its one or two column groups, group-major and
+//     slab-minor.  The two or three streams are read XU_OCC_LOAD slabs at a time by 16-byte scalar loads, the next chunk
+//     requested while the current one is worked on (a zero chunk stands behind every stream, ff_schedule.hpp).
+//   * Per slab the union mask m is scalar.  m == 0: nothing is read for the slab, neither presence words nor lengths.
+//     Else the set bits of m are walked lowest first (find-first-set, clear-lowest: scalar, wave-uniform) and each runs
+//     what a branch runs in the dense form: lj / lnj by masking and XuBranch<J>::run, as they stand.
+//   * A non-empty slab's column words, row words and lengths are requested while the slab before it is worked on --
+//     when that slab's mask says so.  The lengths travel as ONE 256-byte coalesced vector load per slab from a copy kept
+//     in the order the lanes want them (lane k < 32: low word of the slab's k-th length; lane 32 + k: its high word;
+//     ff_plan.d_xu_len_words) and reach the scalar side by two v_readlane_b32 with the bit's index: no memory
+//     operation and no wait inside the walk over the bits, and two registers (current and next) instead of the scalar
+//     block fetch of the dense form, which assumes that every row is visited.  The other way -- scalar loads of the
+//     next set bits' lengths while the current branch's block runs -- needs the request and the wait apart, which the
+//     compiler cannot be told (the dense form's comment on XU_LEN_STEP); waited for on the spot it is a round trip of
+//     the scalar cache per visited branch.
+typedef uint32_t xu_u32x4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(4))) xu_u32x4 *xu_c128;
+static_assert(sizeof(xu_u32x4) == XU_OCC_LOAD * sizeof(uint32_t), "pair_exact_unw_skip_kernel: a chunk of occupancy words is one 16-byte load");
+
+template <int J>
+__device__ __forceinline__ void exact_unw_skip_tile(const uint32_t *__restrict__ Xb, int64_t ldx,
+                                                    const uint32_t *__restrict__ len_words, int n_chunks,
+                                                    const uint32_t *__restrict__ rowocc, const uint32_t *__restrict__ colocc,
+                                                    int64_t occ_stride, int i0, int j0, int64_t row_begin, int64_t row_end,
+                                                    int64_t slot_begin, double *__restrict__ out)
+{
+    constexpr int H = XU_TILE_H;
+    const uint32_t lane = threadIdx.x & 63;
+    double res[H][J], com[H][J];
+#pragma unroll
+    for (int r = 0; r < H; ++r)
+#pragma unroll
+        for (int t = 0; t < J; ++t) res[r][t] = com[r][t] = 0.0;
+    const uint32_t *pj = Xb + j0;  // (uniform bases, the lane as a 32-bit offset: one address register for every vector load)
+    xu_c32 pi = (xu_c32)(Xb + i0);
+    xu_c128 pr = (xu_c128)(rowocc + (int64_t)(i0 / H) * occ_stride);
+    xu_c128 pc = (xu_c128)(colocc + (int64_t)(j0 / 64) * occ_stride);
+    const int64_t chunk_stride = occ_stride / XU_OCC_LOAD;
+    auto masks = [&](int64_t c) {
+        xu_u32x4 m = pr[c] | pc[c];
+        if (J == 2) m |= pc[chunk_stride + c];
+        return m;
+    };
+    uint32_t wj[J], wi[H], lv, wjn[J], win[H], lvn = 0;
+#pragma unroll
+    for (int t = 0; t < J; ++t) wjn[t] = 0;
+#pragma unroll
+    for (int r = 0; r < H; ++r) win[r] = 0;
+    // slab s's column words, row words and lengths, for the trip behind this one
+    auto request = [&](int64_t s) {
+#pragma unroll
+        for (int t = 0; t < J; ++t) wjn[t] = pj[s * ldx + 64 * t + lane];
+#pragma unroll
+        for (int r = 0; r < H; ++r) win[r] = pi[s * ldx + r];
+        lvn = len_words[s * (2 * XU_SLAB) + lane];
+    };
+    static_assert(2 * XU_SLAB == 64, "exact_unw_skip_tile: a slab's length words are one load of the wave");
+    xu_u32x4 cur = masks(0);
+    if (cur[0]) request(0);
+    for (int c = 0; c < n_chunks; ++c) {
+        const xu_u32x4 nxt = masks((int64_t)c + 1);  // (c + 1 == n_chunks: the zero chunk)
+        const uint32_t mm[XU_OCC_LOAD + 1] = {cur[0], cur[1], cur[2], cur[3], nxt[0]};
+#pragma unroll
+        for (int q = 0; q < XU_OCC_LOAD; ++q) {
+#pragma unroll
+            for (int t = 0; t < J; ++t) wj[t] = wjn[t];
+#pragma unroll
+            for (int r = 0; r < H; ++r) wi[r] = win[r];
+            lv = lvn;
+            if (mm[q + 1]) request((int64_t)c * XU_OCC_LOAD + q + 1);
+            for (uint32_t m = mm[q]; m; m &= m - 1) {
+                const uint32_t k = (uint32_t)__builtin_ctz(m);
+                const uint32_t llo = (uint32_t)__builtin_amdgcn_readlane((int)lv, (int)k);
+                const uint32_t lhi = (uint32_t)__builtin_amdgcn_readlane((int)lv, (int)(k + XU_SLAB));
+                double lj[J], lnj[J];
+#pragma unroll
+                for (int t = 0; t < J; ++t) {
+                    const uint32_t b = (uint32_t)__builtin_amdgcn_sbfe((int)wj[t], k, 1);  // all ones iff j has the branch
+                    lj[t] = __hiloint2double((int)(lhi & b), (int)(llo & b));
+                    lnj[t] = __hiloint2double((int)(lhi & ~b), (int)(llo & ~b));
+                }
+                XuBranch<J>::run(res, com, lj, lnj, wi, k);
+            }
+        }
+        cur = nxt;
+    }
+    xu_write_out<J>(res, com, i0, j0, row_begin, row_end, slot_begin, out);
+}
+
+// One wave per tile, as the dense form; the same tiles.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8)))
+void pair_exact_unw_skip_kernel(const uint32_t *__restrict__ Xb, int64_t ldx, const uint32_t *__restrict__ len_words, int n_chunks,
+                                const uint32_t *__restrict__ rowocc, const uint32_t *__restrict__ colocc, int64_t occ_stride,
+                                const XUTile *__restrict__ tiles, int64_t row_begin, int64_t row_end, int64_t slot_begin,
+                                double *__restrict__ out)
+{
+    const XUTile tile = tiles[blockIdx.x];
+    const int i0 = __builtin_amdgcn_readfirstlane(tile.i0), j0 = __builtin_amdgcn_readfirstlane(tile.j0);
+    if (__builtin_amdgcn_readfirstlane(tile.jn) == 2)
+        exact_unw_skip_tile<2>(Xb, ldx, len_words, n_chunks, rowocc, colocc, occ_stride, i0, j0, row_begin, row_end, slot_begin, out);
+    else
+        exact_unw_skip_tile<1>(Xb, ldx, len_words, n_chunks, rowocc, colocc, occ_stride, i0, j0, row_begin, row_end, slot_begin, out);
+}
+
+// What the skipping form would do on the shard's tiles, counted exactly: counts[0] += the (tile, row) cells it visits
+// (the set bits of every tile's union masks), counts[1] += the (tile, slab) cells that are not empty, counts[2] += the
+// visited cells times the tile's column groups (the terms issued are 64 * XU_TILE_H times that).  A wave per tile.
+enum { XU_CNT_ROWS = 0, XU_CNT_SLABS = 1, XU_CNT_ROWS_J = 2, XU_CNT_N = 3 };
+__global__ __launch_bounds__(64)
+void xu_visit_count_kernel(const XUTile *__restrict__ tiles, const uint32_t *__restrict__ rowocc, const uint32_t *__restrict__ colocc,
+                           int64_t occ_stride, int n_slabs, unsigned long long *__restrict__ counts)
+{
+    const XUTile tile = tiles[blockIdx.x];
+    const uint32_t *pr = rowocc + (int64_t)(tile.i0 / XU_TILE_H) * occ_stride, *pc = colocc + (int64_t)(tile.j0 / 64) * occ_stride;
+    uint32_t rows = 0, slabs = 0;
+    for (int s = threadIdx.x; s < n_slabs; s += 64) {
+        uint32_t m = pr[s] | pc[s];
+        if (tile.jn == 2) m |= pc[occ_stride + s];
+        rows += (uint32_t)__popc(m);
+        slabs += m != 0;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        rows += __shfl_down(rows, off, 64);
+        slabs += __shfl_down(slabs, off, 64);
+    }
+    if (threadIdx.x == 0 && slabs) {
+        atomicAdd(&counts[XU_CNT_ROWS], (unsigned long long)rows);
+        atomicAdd(&counts[XU_CNT_SLABS], (unsigned long long)slabs);
+        atomicAdd(&counts[XU_CNT_ROWS_J], (unsigned long long)rows * (unsigned)tile.jn);
+    }
 }

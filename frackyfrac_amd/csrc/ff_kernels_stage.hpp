@@ -213,6 +213,22 @@ __global__ void stage_xbits_kernel(const int64_t *__restrict__ indptr, const int
     }
 }
 
+// The group-occupancy words of pair_exact_unw_skip_kernel from the presence bits: a wave per (64-sample column group,
+// slab) ORs its 64 words -- by row groups of XU_TILE_H samples, then all of them -- into rowocc[row group][slab] and
+// colocc[column group][slab] (group-major, `stride` words per group; the words behind the last slab stay zero).
+__global__ __launch_bounds__(64)
+void xu_occupancy_kernel(const uint32_t *__restrict__ Xb, int64_t ldx, int64_t stride, uint32_t *__restrict__ rowocc,
+                         uint32_t *__restrict__ colocc)
+{
+    const int64_t s = blockIdx.x, g = blockIdx.y;
+    const int lane = threadIdx.x;
+    uint32_t w = Xb[s * ldx + g * 64 + lane];
+    for (int off = 1; off < XU_TILE_H; off <<= 1) w |= __shfl_xor(w, off, 64);
+    if (lane % XU_TILE_H == 0) rowocc[(g * (64 / XU_TILE_H) + lane / XU_TILE_H) * stride + s] = w;
+    for (int off = XU_TILE_H; off < 64; off <<= 1) w |= __shfl_xor(w, off, 64);
+    if (lane == 0) colocc[g * stride + s] = w;
+}
+
 
 // ---- rare rows of a sparse table: lists by sample block for pair_low_kernel (ff_schedule.hpp LOW_*) ----------------
 // Layout: BLOCK-major.  ptr[block][r] .. ptr[block][r + 1] are the entries (sample, staged value) of rare row r among the

@@ -117,6 +117,12 @@ struct ff_plan {
     int xu_slabs = 0;
     ff::sched::XUTile *d_xutiles = nullptr;
     int n_xutiles = 0;
+    // its row-skipping form (pair_exact_unw_skip_kernel): the OR of the presence words per slab of every 8-sample row
+    // group and every 64-sample column group, [group][xu_occ_stride] (ff_schedule.hpp XU_OCC_*); they do not depend on the shard
+    uint32_t *d_xu_rowocc = nullptr, *d_xu_colocc = nullptr;
+    int64_t xu_occ_stride = 0;
+    uint32_t *d_xu_len_words = nullptr;  // the lengths by staged row once more, as a wave loads them: per slab its 32 low words, then its 32 high words
+    bool xu_skip = false;  // the shard's tiles run the skipping form (chosen per schedule: FF_XU_SKIP, or the estimate)
     // timing: the events of every timed run since the last collect -- around the pair reduction, and between the matrix
     // rows' kernel and the rare rows' (recorded only where the plan is split: `split` says which; the rare rows' kernel
     // runs second in a weighted plan, first in an unweighted one)

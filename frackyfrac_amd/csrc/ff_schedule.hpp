@@ -102,6 +102,25 @@ inline int64_t xu_slabs(int64_t R) { return (std::max<int64_t>(R, 1) + XU_SLAB -
 inline int64_t xu_alloc_slabs(int64_t R) { return xu_slabs(R) + XU_PAD_SLABS; }
 inline int64_t xu_alloc_lengths(int64_t R) { return xu_slabs(R) * XU_SLAB + XU_LEN_PAD; }
 inline int64_t xu_ld(int64_t N) { return round_up(std::max<int64_t>(N, 1), 64 * XU_JMAX); }  // samples per slab row
+//   pair_exact_unw_skip_kernel walks group-occupancy words instead: per slab the OR of the presence words of every
+//   XU_TILE_H-sample row group and of every 64-sample column group, GROUP-major and slab-minor, so that a tile's two or
+//   three streams are read XU_OCC_LOAD words (one 16-byte scalar load per stream) at a time.  The load of the chunk
+//   BEHIND the one worked on is requested ahead, whatever the slab count: a stream is padded with zeros to whole
+//   chunks plus XU_OCC_PAD_CHUNKS of them.  A zero word is an empty slab: the kernel reads neither presence words nor
+//   lengths for it, so it never leaves the staged slabs.
+constexpr int XU_OCC_LOAD = 4;
+constexpr int XU_OCC_PAD_CHUNKS = 1;
+static_assert(XU_OCC_LOAD * sizeof(uint32_t) == 16 && XU_OCC_PAD_CHUNKS >= 1, "the occupancy streams' zero chunk must cover pair_exact_unw_skip_kernel's load ahead");
+inline int64_t xu_occ_chunks(int64_t R) { return (xu_slabs(R) + XU_OCC_LOAD - 1) / XU_OCC_LOAD; }  // chunks the walk covers
+inline int64_t xu_occ_stride(int64_t R) { return (xu_occ_chunks(R) + XU_OCC_PAD_CHUNKS) * XU_OCC_LOAD; }  // words per group
+inline int64_t xu_occ_row_groups(int64_t N) { return xu_ld(N) / XU_TILE_H; }
+inline int64_t xu_occ_col_groups(int64_t N) { return xu_ld(N) / 64; }
+static_assert(64 % XU_TILE_H == 0, "a 64-sample column group holds whole row groups");
+//   what the two forms cost, in device-nanoseconds (kernel time x 1 for the whole device): the dense form per (tile, row),
+//   the skipping form per visited (tile, row) and per (tile, slab) that is not empty (measured: DESIGN 4.11)
+constexpr double XU_NS_DENSE_ROW = 0.0456;
+constexpr double XU_NS_SKIP_ROW = 0.0532;
+constexpr double XU_NS_SKIP_SLAB = 0.0111;
 struct XUTile {
     int32_t i0, j0;  // rows i0 .. i0 + XU_TILE_H - 1, columns j0 + 64 t + lane, t < jn
     int32_t jn;      // 64-sample column groups: 1 or 2 (the last tile of a row block may be the narrower one)

@@ -93,7 +93,9 @@ typedef enum ff_precision {
                                  reference never touches a branch neither sample of a pair
                                  has); weighted about 4x slower
                                  than FIXED32, unweighted about 2x slower than the vector-ALU
-                                 FIXED32 path (40x slower than the matrix cores)              */
+                                 FIXED32 path (40x slower than the matrix cores); on a sparse
+                                 table the unweighted kernel runs only the branches some sample
+                                 of a pair tile has (ff_plan_info.active_fraction; same bits) */
 } ff_precision;
 
 typedef struct ff_options {
@@ -225,7 +227,11 @@ typedef struct ff_plan_info {
                                   re-computed exactly (the rule queues everything under 1); infinity: none */
     double active_fraction;    /* FIXED32 weighted: share of the shard's (32-sample block, staged row) cells in
                                   which some sample has the branch -- what pair_sad_sparse_kernel walks (it skips
-                                  the rest) and what decides between it and the dense kernel; 1 where not counted */
+                                  the rest) and what decides between it and the dense kernel.
+                                  FF_KERNEL_EXACT_F64_UNW: share of the shard's (pair tile, staged row) cells in which some
+                                  sample of the tile has the branch, when the row-skipping form runs (it visits those and
+                                  no others; `elements` counts the terms it issues, `n_items` the (tile, 32-row slab) cells
+                                  that are not empty); 1 on the dense form.  1 where not counted */
     int64_t rare_rows;         /* FIXED32 on a sparse table: staged rows kept OUT of the matrix (few samples reach
                                   them) and reduced over the pairs that both have them -- by pair_low_kernel
                                   (weighted), by pair_low_unw_kernel ahead of the matrix cores (unweighted: `kernel`
@@ -246,7 +252,10 @@ typedef enum ff_kernel {
                                      of it (few hundred samples): 32 x 32 tiles, one launch per pass     */
     FF_KERNEL_EXACT_F64_UNW = 5,  /* pair_exact_unw_kernel: EXACT64 unweighted from presence bits -- the
                                      reference's two chains of binary64 additions per pair and no other
-                                     arithmetic (unifrac.go:144-171)                                      */
+                                     arithmetic (unifrac.go:144-171); or its row-skipping form,
+                                     pair_exact_unw_skip_kernel, which leaves out the branches none of a tile's
+                                     samples has (they add +0.0: same bits) where an exact count of what it
+                                     would visit says it is faster (active_fraction < 1 says it runs)     */
     FF_KERNEL_WALK_F64 = 6,       /* pair_walk_kernel: the reference's merge walk itself, a thread per pair,
                                      over lists as they stand (FF_FLAG_UNSORTED_WALK)                     */
     FF_KERNEL_EXACT_F64_SKIP = 7  /* pair_exact64_skip_kernel: EXACT64 weighted; a branch a row has not adds
