@@ -61,6 +61,12 @@ func ffDeliver(user unsafe.Pointer, slotBegin C.int64_t, dists *C.double, n C.in
 	return 1
 }
 
+// Generalized UniFrac d(alpha), 0 <= alpha <= 1 (FF_FLAG_GENERALIZED; the reference has no such metric): a maintainer
+// who adds a -g flag puts
+//	C.ff_options_set_alpha(&o, C.double(*alpha))
+// behind `o.weighted = 1` in the two functions below; C.ff_options_alpha(&o) reads it back (NaN without the flag).
+// alpha = 1 is weighted UniFrac itself, bit for bit; the flag needs `weighted` and excludes -l (FF_FLAG_UNSORTED_WALK).
+
 // unifracDistsGPU replaces unifracDists (frcfrc/unifrac.go:209-228).  The second result reports
 // what went wrong, if anything, once the sequence has been ranged over (the bufio.Scanner
 // pattern: unifracDists itself has no error path, a device has); the caller hands it to

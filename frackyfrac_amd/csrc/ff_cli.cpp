@@ -6,7 +6,7 @@
 // (frcfrc.go:78-86), the same stderr phase lines and the same output: one
 // distance per line in IterPairs order, formatted like fmt.Fprintln (frcfrc.go:58-62).
 // Errors print "ERROR: <msg>" and exit 2 (common/common.go:13-18).
-// Extensions (not in the reference): -precision auto|fixed32|exact64, -stats, -gpus N.
+// Extensions (not in the reference): -precision auto|fixed32|exact64, -stats, -gpus N, -g ALPHA (generalized UniFrac).
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -27,6 +27,7 @@ void usage()
 {
     fputs(USAGE, stderr);
     // flag.PrintDefaults(): flags in lexical order
+    fputs("  -g float\n    \tGeneralized UniFrac d(alpha), alpha in [0, 1]; needs -w (default: alpha = 1, weighted UniFrac itself)\n", stderr);
     fputs("  -gpus int\n    \tNumber of GPUs to shard the pair space over (default 1)\n", stderr);
     fputs("  -i string\n    \tPath to input file (default stdin)\n", stderr);
     fputs("  -l\tLeave abundance values unnormalized (default normalize each sample to sum up to 1)\n", stderr);
@@ -51,6 +52,8 @@ struct Flags {
     bool weighted = false, sparse = false, nnorm = false, stats = false, lcompat = false, lsorted = false;
     long nt = 1, gpus = 1;
     bool nt_given = false;
+    double alpha = 1.0;
+    bool alpha_given = false;
 };
 
 bool parse_bool(const std::string &v, bool *out)
@@ -114,7 +117,7 @@ int parse_flags(int argc, char **argv, Flags *f)
         }
         std::string *sp = name == "i" ? &f->in : name == "o" ? &f->out : name == "t" ? &f->tree
                           : name == "precision" ? &f->precision : nullptr;
-        if (!sp && name != "p" && name != "gpus") {
+        if (!sp && name != "p" && name != "gpus" && name != "g") {
             fprintf(stderr, "flag provided but not defined: -%s\n", name.c_str());
             usage();
             return 2;
@@ -129,6 +132,14 @@ int parse_flags(int argc, char **argv, Flags *f)
         }
         if (sp) {
             *sp = value;
+        } else if (name == "g") {
+            const char *why = nullptr;
+            if (!ff::go_parse_float(value.data(), value.data() + value.size(), &f->alpha, &why)) {
+                fprintf(stderr, "invalid value %s for flag -g: parse error\n", ff::go_quote(value).c_str());
+                usage();
+                return 2;
+            }
+            f->alpha_given = true;
         } else {
             char *end = nullptr;
             errno = 0;
@@ -187,6 +198,8 @@ extern "C" int ff_frcfrc_main(int argc, char **argv)
     if (f.lcompat && !f.nnorm) return die("-l-compat can only be used with -l");
     if (f.lsorted && !f.nnorm) return die("-l-sorted can only be used with -l");
     if (f.lsorted && f.lcompat) return die("-l-sorted and -l-compat exclude each other");
+    if (f.alpha_given && !f.weighted) return die("-g can only be used with weighted unifrac");
+    if (f.alpha_given && !(f.alpha >= 0.0 && f.alpha <= 1.0)) return die(("bad alpha: " + ff::go_v(f.alpha)).c_str());
     if (f.gpus < 1 || f.gpus > 64) {
         char m[64];
         snprintf(m, sizeof m, "bad number of GPUs: %ld", f.gpus);
@@ -195,6 +208,7 @@ extern "C" int ff_frcfrc_main(int argc, char **argv)
     ff_options opt;
     ff_options_default(&opt);
     opt.weighted = f.weighted;
+    if (f.alpha_given) ff_options_set_alpha(&opt, f.alpha);
     if (f.precision == "auto") opt.precision = FF_PRECISION_AUTO;
     else if (f.precision == "fixed32") opt.precision = FF_PRECISION_FIXED32;
     else if (f.precision == "exact64") opt.precision = FF_PRECISION_EXACT64;
@@ -408,7 +422,7 @@ extern "C" int ff_frcfrc_main(int argc, char **argv)
                 "\"failed\": %lld, \"worst_rel_err\": %.3g, \"min_headroom\": %s}, \"seconds\": {\"tree\": %.3f, "
                 "\"load\": %.3f, \"validate\": %.3f, \"open\": %.3f, \"convert\": %.3f, \"distances\": %.3f, \"write\": %.3f, \"close\": %.3f}, "
                 "\"detail\": {\"plan\": %.3f, \"retarget\": %.3f, \"kernels\": %.3f, \"format\": %.3f, \"text_copy\": %.3f, \"text_write\": %.3f, \"text_bytes\": %lld}}\n",
-                info.precision == FF_PRECISION_FIXED32 ? "fixed32" : "exact64", info.scale_log2,
+                info.precision == FF_PRECISION_FIXED32 ? "fixed32" : info.precision == FF_PRECISION_FLOAT32 ? "float32" : "exact64", info.scale_log2,
                 info.lengths_exact,
                 info.precision == FF_PRECISION_EXACT64 || (!f.weighted && info.lengths_exact) ? "true" : "false",
                 (long long)info.n_tiles, (long long)info.n_items,

@@ -30,6 +30,7 @@ using namespace ff::sched;
 #include "ff_kernels_finish.hpp"
 #include "ff_kernels_exact_unw.hpp"
 #include "ff_kernels_exact_w.hpp"
+#include "ff_kernels_general.hpp"
 #include "ff_kernels_low.hpp"
 #include "ff_kernels_low_unw.hpp"
 
@@ -301,10 +302,28 @@ int refine_blocks_per_cu()
     return n;
 }
 
+// One launch of pair_general_kernel: the form of t = s^(alpha - 1) and the tile height are template parameters.
+int launch_general(ff_plan *pl, hipStream_t st, double *d_out, char *err, size_t errlen)
+{
+    const ff_plan_info &inf = pl->info;
+    if (pl->n_xtiles <= 0) return FF_OK;
+    if (!g_tile_height_ok(pl->x_tile_h)) return ff::fail(FF_ERR_INTERNAL, err, errlen, "generalized: no kernel for tile height %d", pl->x_tile_h);
+    const bool h8 = pl->x_tile_h == 8;
+    auto kern = pl->g_alpha == 0.0   ? (h8 ? pair_general_kernel<G_ZERO, 8> : pair_general_kernel<G_ZERO, 16>)
+                : pl->g_alpha == 0.5 ? (h8 ? pair_general_kernel<G_HALF, 8> : pair_general_kernel<G_HALF, 16>)
+                                     : (h8 ? pair_general_kernel<G_ANY, 8> : pair_general_kernel<G_ANY, 16>);
+    kern<<<dim3((unsigned)((pl->n_xtiles + 3) / 4)), dim3(256), 0, st>>>(pl->d_GT, inf.ld, pl->d_len_rows ? pl->d_len_rows : pl->d_len, inf.n_rows,
+                                                                       (float)(pl->g_alpha - 1.0), pl->d_xtiles, pl->n_xtiles, inf.row_begin,
+                                                                       inf.row_end, inf.slot_begin, d_out);
+    FF_HIP(hipGetLastError());
+    return FF_OK;
+}
+
 // One launch of the EXACT64 pair kernel with the plan's tile height.
 int launch_exact64(ff_plan *pl, hipStream_t st, double *d_out, char *err, size_t errlen)
 {
     const ff_plan_info &inf = pl->info;
+    if (pl->general) return launch_general(pl, st, d_out, err, errlen);
     if (pl->xu) {
         if (pl->n_xutiles > 0 && pl->xu_skip)
             pair_exact_unw_skip_kernel<<<dim3((unsigned)pl->n_xutiles), dim3(64), 0, st>>>(pl->d_Xbits, pl->xu_ldx, pl->d_xu_len_words,
@@ -378,8 +397,8 @@ int upload_exact64_tiles(ff_plan *pl, int h, char *err, size_t errlen)
                         xt.size(), ((size_t)1 << 26) - 1);
     pl->n_xtiles = (int)xt.size();
     pl->x_tile_h = h;
-    pl->x_skip = pl->weighted && inf.n_rows > 0 && env_int("FF_X_SKIP", 1) != 0 && (h == 8 || h == 12 || h == 16);
-    inf.kernel = pl->x_skip ? FF_KERNEL_EXACT_F64_SKIP : FF_KERNEL_EXACT_F64;
+    pl->x_skip = !pl->general && pl->weighted && inf.n_rows > 0 && env_int("FF_X_SKIP", 1) != 0 && (h == 8 || h == 12 || h == 16);
+    inf.kernel = pl->general ? FF_KERNEL_GENERAL_F32 : pl->x_skip ? FF_KERNEL_EXACT_F64_SKIP : FF_KERNEL_EXACT_F64;
     FF_HIP(hipMalloc(&pl->d_xtiles, sizeof(XTile) * std::max<size_t>(xt.size(), 1)));
     if (!xt.empty()) FF_HIP(hipMemcpy(pl->d_xtiles, xt.data(), sizeof(XTile) * xt.size(), hipMemcpyHostToDevice));
     inf.n_wave_slots = (int64_t)xt.size();
@@ -462,6 +481,7 @@ int schedule_exact64(ff_plan *pl, char *err, size_t errlen)
         const int64_t resident = (int64_t)inf.n_compute_units * 4 * 8;
         bool small = false;
         for (int cand : {4, 8}) {
+            if (pl->general && !g_tile_height_ok(cand)) continue;  // (pair_general_kernel: G_TILE_HEIGHTS)
             std::vector<Tile> count;
             build_tiles(inf.n_samples, inf.row_begin, inf.row_end, cand, X_TILE_J, false, &count);
             if ((int64_t)count.size() * 100 <= resident * (cand == 4 ? 55 : 45)) {
@@ -482,9 +502,11 @@ int schedule_exact64(ff_plan *pl, char *err, size_t errlen)
             double best_score = 0;
             // (weighted: pair_exact64_skip_kernel has the heights 8, 12 and 16; at C3's shape 25.5 / 21.2 / 22.4 ms with
             // 16.25 / 10.9 / 8.1 tiles per SIMD, i.e. per tile-round worth 0.83 / 0.96 / 1)
-            const bool skip = pl->weighted && env_int("FF_X_SKIP", 1) != 0;
+            // (pair_general_kernel has the row chains of the skip kernel at the heights 8 and 16, and takes its weights)
+            const bool skip = pl->general || (pl->weighted && env_int("FF_X_SKIP", 1) != 0);
             for (int cand : {8, 10, 12, 14, 16}) {
                 if (skip && cand != 8 && cand != 12 && cand != 16) continue;
+                if (pl->general && !g_tile_height_ok(cand)) continue;
                 std::vector<Tile> count;
                 build_tiles(inf.n_samples, inf.row_begin, inf.row_end, cand, X_TILE_J, false, &count);
                 const double avg = (double)count.size() / simds;
@@ -498,7 +520,7 @@ int schedule_exact64(ff_plan *pl, char *err, size_t errlen)
             }
         }
         for (int cand : X_TILE_HEIGHTS)
-            if (cand == forced) h = forced;
+            if (cand == forced && (!pl->general || g_tile_height_ok(cand))) h = forced;
         pl->x_tile_h = h;
     }
     return upload_exact64_tiles(pl, pl->x_tile_h, err, errlen);

@@ -1048,6 +1048,35 @@ int stage_for_exact64(StageCtx &x, char *err, size_t errlen)
     return schedule_exact64(pl, err, errlen);
 }
 
+// Generalized UniFrac, alpha != 1: the branch-major matrix of (x, l x^alpha) cells -- 8 bytes a cell, as EXACT64
+// weighted -- and the tiles of pair_general_kernel (the EXACT64 geometry at its own heights).
+int stage_for_general(StageCtx &x, double alpha, char *err, size_t errlen)
+{
+    FF_STAGE_NAMES;
+    pl->general = true;
+    pl->g_alpha = alpha;
+    inf.precision = FF_PRECISION_FLOAT32;
+    inf.kernel = FF_KERNEL_GENERAL_F32;
+    const int64_t ld = round_up(std::max<int64_t>(N, 1), X_TILE_J);
+    inf.ld = ld;
+    inf.rows_padded = R;
+    // (+ G_VALUES_PAD cells: a tile in the last 64 columns reads up to H - 1 cells past the last row's end)
+    const size_t gt_bytes = sizeof(float2) * ((size_t)std::max<int64_t>(R, 1) * (size_t)ld + G_VALUES_PAD);
+    inf.staged_bytes = (double)gt_bytes;
+    FF_ALLOC(pl->d_GT, gt_bytes, "the staged (x, l x^alpha) matrix");
+    FF_HIP(hipMemset(pl->d_GT, 0, gt_bytes));
+    if (N > 0 && nnz > 0)
+        stage_general_kernel<<<dim3((unsigned)N), dim3(256)>>>(d_indptr, d_ids, d_abnd, d_len, alpha, row_of.p, pl->d_GT, ld);
+    FF_HIP(hipGetLastError());
+    if (row_of.p) {  // treeDists by staged row
+        std::vector<double> lr((size_t)R);
+        for (int64_t r = 0; r < R; ++r) lr[(size_t)r] = c->h_len[(size_t)branch_of_row[(size_t)r]];
+        FF_HIP(hipMalloc(&pl->d_len_rows, sizeof(double) * (size_t)std::max<int64_t>(R, 1)));
+        if (R > 0) FF_HIP(hipMemcpy(pl->d_len_rows, lr.data(), sizeof(double) * (size_t)R, hipMemcpyHostToDevice));
+    }
+    return schedule_exact64(pl, err, errlen);
+}
+
 }  // namespace
 
 // Stages the device-resident flat nodes and builds the schedule.  Takes ownership of *c.
@@ -1101,6 +1130,19 @@ int plan_build(const ff_options *o, DeviceCsr *c, const hipDeviceProp_t &prop, f
     const int64_t R = x.R;
     Quant &q = x.q;
     inf.n_rows = R;
+
+    // Generalized UniFrac: alpha = 1 is the weighted path itself and goes on below as if the flag were clear; every
+    // other alpha ignores `precision` and takes pair_general_kernel.  Nothing to refine or audit: the flat nodes go.
+    double alpha = 1.0;
+    if (ff::general_alpha(o, &alpha)) {
+        rc = stage_for_general(x, alpha, err, errlen);
+        if (rc) return rc;
+        FF_HIP(hipDeviceSynchronize());
+        free_and_null(pl->d_indptr);
+        free_and_null(pl->d_ids);
+        free_and_null(pl->d_abnd);
+        return FF_OK;
+    }
 
     int prec = o->precision;
     const bool is_auto = prec == FF_PRECISION_AUTO;

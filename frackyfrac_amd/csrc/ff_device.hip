@@ -122,6 +122,7 @@ void plan_free_device(ff_plan *pl)
     (void)hipFree(pl->d_ptiles);
     (void)hipFree(pl->d_ptile_ptr);
     (void)hipFree(pl->d_DT);
+    (void)hipFree(pl->d_GT);
     (void)hipFree(pl->d_len);
     (void)hipFree(pl->d_len_rows);
     (void)hipFree(pl->d_host_out);
@@ -208,8 +209,12 @@ int ff_plan_create(const ff_problem *p, const ff_options *o, ff_plan **plan, cha
         return ff::fail(FF_ERR_ARG, err, errlen, "bad shard %d of %d", o->rank, o->world);
     if (o->precision < FF_PRECISION_AUTO || o->precision > FF_PRECISION_EXACT64)
         return ff::fail(FF_ERR_ARG, err, errlen, "bad precision %d", o->precision);
-    if ((o->flags & ~FF_FLAG_UNSORTED_WALK) != 0) return ff::fail(FF_ERR_ARG, err, errlen, "unknown flags %d", o->flags);
-    int rc = validate_problem(p, err, errlen, (o->flags & FF_FLAG_UNSORTED_WALK) != 0);
+    if ((o->flags & ~(FF_FLAG_UNSORTED_WALK | FF_FLAG_GENERALIZED)) != 0) return ff::fail(FF_ERR_ARG, err, errlen, "unknown flags %d", o->flags);
+    int rc = ff::check_alpha(o, err, errlen);
+    if (rc) return rc;
+    rc = validate_problem(p, err, errlen, (o->flags & FF_FLAG_UNSORTED_WALK) != 0);
+    if (rc) return rc;
+    rc = ff::check_general_values(o, p->branch_len, p->n_branches, "branch length", err, errlen);  // (abundances: validate_problem)
     if (rc) return rc;
     auto *pl = new ff_plan();
     rc = plan_create_impl(p, o, pl, err, errlen);
@@ -666,6 +671,12 @@ int ff_plan_create_from_leaves(const ff_tree *tree, int64_t n_samples, const int
     if (reference_l) {
         o_walk.flags |= FF_FLAG_UNSORTED_WALK;
         o = &o_walk;
+    }
+    {
+        int rc = ff::check_alpha(o, err, errlen);
+        if (rc == FF_OK) rc = ff::check_general_values(o, tree->dist.data(), B, "branch length", err, errlen);
+        if (rc == FF_OK) rc = ff::check_general_values(o, leaf_val, leaf_ptr[n_samples], "leaf value", err, errlen);
+        if (rc) return rc;
     }
     auto *pl = new ff_plan();
     hipDeviceProp_t prop;

@@ -22,6 +22,14 @@ namespace ff {
 int fail(int code, char *err, size_t errlen, const char *fmt, ...)
     __attribute__((format(printf, 4, 5)));
 
+// Generalized UniFrac (FF_FLAG_GENERALIZED; all three are no-ops without the flag).  check_alpha: the option's own
+// conditions -- alpha in [0, 1], weighted, no unsorted walk.  general_alpha: the plan takes pair_general_kernel (the
+// flag with an alpha other than 1, which is the weighted path itself).  check_general_values: the bound of the
+// binary32 terms needs non-negative finite branch lengths and abundances.
+int check_alpha(const ff_options *o, char *err, size_t errlen);
+bool general_alpha(const ff_options *o, double *alpha);
+int check_general_values(const ff_options *o, const double *v, int64_t n, const char *what, char *err, size_t errlen);
+
 // Go's %q for a string, Go's %v for a float64, Go's %f for a float64.
 std::string go_quote(const std::string &s);
 std::string go_v(double f);

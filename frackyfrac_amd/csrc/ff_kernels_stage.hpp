@@ -82,6 +82,26 @@ __global__ void stage_exact64_kernel(const int64_t *__restrict__ indptr,
     }
 }
 
+// Stage generalized UniFrac (pair_general_kernel): per flat node the cell (x, p), x = the abundance rounded once to
+// binary32, p = l * x^alpha -- the whole term of a pair in which only this sample has the branch -- evaluated in
+// binary64 and rounded once (alpha = 0: l itself).  A positive x under the smallest normal binary32 number is staged
+// as that number: the kernel's reciprocal, square root and logarithm instructions take no denormals, and presence is
+// what an abundance that small amounts to.
+__global__ void stage_general_kernel(const int64_t *__restrict__ indptr, const int32_t *__restrict__ branch_id,
+                                     const double *__restrict__ abnd, const double *__restrict__ branch_len, double alpha,
+                                     const int32_t *__restrict__ row_of, float2 *__restrict__ GT, int64_t ld)
+{
+    const int64_t s = blockIdx.x;
+    const int64_t b0 = indptr[s], b1 = indptr[s + 1];
+    for (int64_t t = b0 + threadIdx.x; t < b1; t += blockDim.x) {
+        const int32_t b = branch_id[t];
+        const double x = abnd[t], l = branch_len[b];
+        if (!(x > 0.0)) continue;  // (a flat node without abundance: the sample has not the branch)
+        const double p = alpha == 0.0 ? l : l * pow(x, alpha);
+        GT[(int64_t)(row_of ? row_of[b] : b) * ld + s] = make_float2(fmaxf((float)x, 1.17549435e-38f), (float)p);
+    }
+}
+
 // W_s = sum_b q_s(b): grid (ld/64, row chunks), one column per lane.
 __global__ void colsum_kernel(const uint32_t *__restrict__ QT, int64_t ld, int64_t rows,
                               int64_t rows_per_block, unsigned long long *__restrict__ W)

@@ -5,7 +5,7 @@
 //   ff_dev_stage.hip   inputs -> HBM: stage A on the device, the flat nodes from the host, the choice of arithmetic,
 //                      branch compaction, the staged matrices / presence bits of every kernel
 //                      (ff_kernels_stage.hpp, ff_kernels_stage_a.hpp).
-//   ff_dev_run.hip     the pair kernels (ff_kernels_pair_sad / mfma / mfma_small / finish / exact_unw.hpp), their work
+//   ff_dev_run.hip     the pair kernels (ff_kernels_pair_sad / mfma / mfma_small / finish / exact_unw / exact_w / general.hpp), their work
 //                      schedules per shard, the refinement queue and the audit, one pass of a plan.
 //
 // Every kernel lives in exactly one of the two files that launch kernels, inside its anonymous namespace (the
@@ -109,6 +109,11 @@ struct ff_plan {
     int n_xtiles = 0;
     int x_tile_h = 0;  // EXACT64 tile height in use (0: not chosen yet)
     bool x_skip = false;  // weighted EXACT64 on pair_exact64_skip_kernel (heights 8, 12, 16; read once per schedule)
+    // generalized UniFrac d(alpha), alpha != 1 (pair_general_kernel): the staged (x, l x^alpha) matrix; lengths by staged
+    // row in d_len_rows / d_len, tiles in d_xtiles, height in x_tile_h (one of G_TILE_HEIGHTS) as for EXACT64
+    bool general = false;
+    double g_alpha = 1.0;
+    float2 *d_GT = nullptr;
     bool walk = false;  // FF_FLAG_UNSORTED_WALK: no staging at all, pair_walk_kernel over the flat nodes as they stand
     // EXACT64 unweighted (pair_exact_unw_kernel): presence bits, lengths by staged row, tiles
     bool xu = false;

@@ -46,6 +46,12 @@ inline int64_t sad_alloc_rows(int64_t R) { return sad_staged_rows(R) + SLACK_ROW
 //   row of the matrix that is up to H - 1 values past the end.
 constexpr int X_VALUES_PAD = 16;
 static_assert(X_VALUES_PAD >= X_TILE_HEIGHTS[sizeof(X_TILE_HEIGHTS) / sizeof(int) - 1] - 1, "EXACT64: padding behind the last row");
+//   pair_general_kernel<.., H> (generalized UniFrac: tiles of the EXACT64 geometry, H one of G_TILE_HEIGHTS) reads H
+//   consecutive (x, p) cells from column i0 of every row in the same way: up to H - 1 cells past the matrix's end.
+constexpr int G_TILE_HEIGHTS[] = {8, 16};
+constexpr int G_VALUES_PAD = 16;
+static_assert(G_VALUES_PAD >= G_TILE_HEIGHTS[sizeof(G_TILE_HEIGHTS) / sizeof(int) - 1] - 1, "generalized: padding behind the last row");
+inline bool g_tile_height_ok(int h) { return h == G_TILE_HEIGHTS[0] || h == G_TILE_HEIGHTS[1]; }
 
 // ---- rare rows of a sparse table (pair_low_kernel) ----
 // A staged row that few samples have a flat node on ("rare": at most N / LOW_SHARE_DIV of them, fewer where the cost

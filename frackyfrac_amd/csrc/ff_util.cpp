@@ -31,6 +31,33 @@ int fail(int code, char *err, size_t errlen, const char *fmt, ...)
     return code;
 }
 
+int check_alpha(const ff_options *o, char *err, size_t errlen)
+{
+    if (!(o->flags & FF_FLAG_GENERALIZED)) return FF_OK;
+    const double alpha = ff_options_alpha(o);
+    if (!(alpha >= 0.0 && alpha <= 1.0)) return fail(FF_ERR_ARG, err, errlen, "bad alpha: %s", go_v(alpha).c_str());
+    if (!o->weighted) return fail(FF_ERR_ARG, err, errlen, "alpha can only be used with weighted unifrac");
+    if (o->flags & FF_FLAG_UNSORTED_WALK)
+        return fail(FF_ERR_ARG, err, errlen, "alpha cannot be used with the unsorted walk (FF_FLAG_UNSORTED_WALK, FF_L_REFERENCE)");
+    return FF_OK;
+}
+
+bool general_alpha(const ff_options *o, double *alpha)
+{
+    if (!(o->flags & FF_FLAG_GENERALIZED)) return false;
+    *alpha = ff_options_alpha(o);
+    return *alpha != 1.0;
+}
+
+int check_general_values(const ff_options *o, const double *v, int64_t n, const char *what, char *err, size_t errlen)
+{
+    if (!(o->flags & FF_FLAG_GENERALIZED)) return FF_OK;
+    for (int64_t k = 0; k < n; ++k)
+        if (!(v[k] >= 0.0) || !std::isfinite(v[k]))
+            return fail(FF_ERR_ARG, err, errlen, "alpha: %s %lld is negative or not finite (%s)", what, (long long)k, go_v(v[k]).c_str());
+    return FF_OK;
+}
+
 std::string go_quote(const std::string &s)
 {
     std::string o = "\"";
@@ -679,6 +706,25 @@ void ff_options_default(ff_options *o)
     o->device = -1;
     o->rank = 0;
     o->world = 1;
+}
+
+void ff_options_set_alpha(ff_options *o, double alpha)
+{
+    if (!o) return;
+    o->flags |= FF_FLAG_GENERALIZED;
+    uint64_t bits;
+    memcpy(&bits, &alpha, sizeof bits);
+    o->reserved[0] = (int32_t)(uint32_t)bits;  // low word first
+    o->reserved[1] = (int32_t)(uint32_t)(bits >> 32);
+}
+
+double ff_options_alpha(const ff_options *o)
+{
+    if (!o || !(o->flags & FF_FLAG_GENERALIZED)) return NAN;
+    const uint64_t bits = (uint64_t)(uint32_t)o->reserved[0] | ((uint64_t)(uint32_t)o->reserved[1] << 32);
+    double alpha;
+    memcpy(&alpha, &bits, sizeof alpha);
+    return alpha;
 }
 
 int ff_cpu_quota(void) { return (int)ff::cpu_quota(); }

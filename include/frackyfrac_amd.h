@@ -86,7 +86,7 @@ typedef enum ff_precision {
                                  sparse table the rows few samples reach leave the matrix of
                                  either and are reduced over the pairs that both have them
                                  (ff_plan_info.rare_rows; same integers again)                */
-    FF_PRECISION_EXACT64 = 2  /* binary64 in the reference's own summation order: bit-for-bit
+    FF_PRECISION_EXACT64 = 2, /* binary64 in the reference's own summation order: bit-for-bit
                                  the reference for every input it accepts (negative, infinite
                                  and NaN branch lengths included: a tree with a non-finite
                                  length is reduced by the literal merge walk, which like the
@@ -96,6 +96,9 @@ typedef enum ff_precision {
                                  FIXED32 path (40x slower than the matrix cores); on a sparse
                                  table the unweighted kernel runs only the branches some sample
                                  of a pair tile has (ff_plan_info.active_fraction; same bits) */
+    FF_PRECISION_FLOAT32 = 3  /* REPORTED ONLY (ff_plan_info.precision of a generalized plan, FF_FLAG_GENERALIZED
+                                 with alpha != 1): binary32 terms summed in binary64, within 1e-6 ABSOLUTE of
+                                 d(alpha).  As a requested precision it is refused ("bad precision")          */
 } ff_precision;
 
 typedef struct ff_options {
@@ -105,7 +108,8 @@ typedef struct ff_options {
     int32_t rank;         /* pair-space shard: this process computes the rows of shard `rank` */
     int32_t world;        /* of `world` equal-work shards (1 = everything); see ff_shard_rows */
     int32_t flags;        /* FF_FLAG_*                                                        */
-    int32_t reserved[2];  /* must be 0                                                        */
+    int32_t reserved[2];  /* must be 0 -- unless FF_FLAG_GENERALIZED is set: then alpha's binary64 bits, low
+                             word first (ff_options_set_alpha writes them, ff_options_alpha reads them)   */
 } ff_options;
 
 /* ff_options.flags.
@@ -117,9 +121,27 @@ typedef struct ff_options {
  * FF_L_REFERENCE in the entry points that flatten, `frcfrc -l -l-compat`) it reproduces the reference
  * bit for bit instead: one thread per pair walks the two lists literally, in binary64. */
 #define FF_FLAG_UNSORTED_WALK 1
+/* FF_FLAG_GENERALIZED: generalized UniFrac d(alpha) (Chen et al. 2012), 0 <= alpha <= 1, carried in reserved[].
+ * With the flat-node abundances x_s(b) >= 0 and the branch lengths l_b >= 0, over the branches with
+ * s = x_i(b) + x_j(b) > 0:
+ *     d(alpha) = sum_b l_b s^alpha (|x_i(b) - x_j(b)| / s)  /  sum_b l_b s^alpha          (0 / 0 = NaN)
+ * alpha = 1 IS weighted UniFrac (unifrac.go:174-205): the plan is the one `weighted = 1` builds without the flag --
+ * same precision policy, same kernels, same bits.  Every other alpha ignores `precision` and runs
+ * pair_general_kernel (FF_KERNEL_GENERAL_F32, reported precision FF_PRECISION_FLOAT32): binary32 terms, binary64
+ * sums, every term non-negative, so that a distance is within (roundings per term + 2) * 2^-24 -- under 1e-6
+ * ABSOLUTE -- of the formula above; a pair's value does not depend on tile height, shard or launch.  Such a plan
+ * has nothing to refine or audit (ff_plan_refined_pairs and ff_plan_audit give zeros).
+ * FF_ERR_ARG, before the device is touched: alpha NaN or outside [0, 1]; weighted == 0; FF_FLAG_UNSORTED_WALK (or
+ * FF_L_REFERENCE) with it; a branch length or an abundance that is negative or not finite (the bound needs
+ * non-negative terms). */
+#define FF_FLAG_GENERALIZED 2
 
 /* Fills *o with the defaults: unweighted, AUTO, current device, rank 0 of 1. */
 void ff_options_default(ff_options *o);
+/* Sets FF_FLAG_GENERALIZED and stores alpha's bits (any value: the entry points validate it). */
+void ff_options_set_alpha(ff_options *o, double alpha);
+/* The alpha of *o; NaN when FF_FLAG_GENERALIZED is clear. */
+double ff_options_alpha(const ff_options *o);
 
 /* Number of output slots for n samples: n*(n-1)/2. */
 int64_t ff_num_pairs(int64_t n_samples);
@@ -189,7 +211,7 @@ typedef struct ff_tree ff_tree; /* section 2 */
 
 /* What the staging decided; read back with ff_plan_info. */
 typedef struct ff_plan_info {
-    int32_t precision;        /* FF_PRECISION_FIXED32 or FF_PRECISION_EXACT64 actually used   */
+    int32_t precision;        /* FF_PRECISION_FIXED32, _EXACT64 or _FLOAT32 actually used     */
     int32_t scale_log2;       /* FIXED32: values are floor(x * 2^scale_log2 + u_branch)       */
     int32_t lengths_exact;    /* FIXED32 unweighted: 1 if every branch length is an exact
                                  multiple of 2^-scale_log2 (results then bit-exact)           */
@@ -258,9 +280,12 @@ typedef enum ff_kernel {
                                      would visit says it is faster (active_fraction < 1 says it runs)     */
     FF_KERNEL_WALK_F64 = 6,       /* pair_walk_kernel: the reference's merge walk itself, a thread per pair,
                                      over lists as they stand (FF_FLAG_UNSORTED_WALK)                     */
-    FF_KERNEL_EXACT_F64_SKIP = 7  /* pair_exact64_skip_kernel: EXACT64 weighted; a branch a row has not adds
+    FF_KERNEL_EXACT_F64_SKIP = 7, /* pair_exact64_skip_kernel: EXACT64 weighted; a branch a row has not adds
                                      l * y twice (unifrac.go:186-187) instead of the six operations of
                                      :191-192 on a zero -- same bits as FF_KERNEL_EXACT_F64               */
+    FF_KERNEL_GENERAL_F32 = 8     /* pair_general_kernel: generalized UniFrac d(alpha), alpha != 1
+                                     (FF_FLAG_GENERALIZED): a branch a row has not adds the column's own term
+                                     l y^alpha to both sums, one where both have it costs one power         */
 } ff_kernel;
 
 /* Stage: quantise / densify the flat nodes into the branch-major matrix in HBM
