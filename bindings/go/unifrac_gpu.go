@@ -62,7 +62,7 @@ func ffDeliver(user unsafe.Pointer, slotBegin C.int64_t, dists *C.double, n C.in
 }
 
 // Generalized UniFrac d(alpha), 0 <= alpha <= 1 (FF_FLAG_GENERALIZED; the reference has no such metric): a maintainer
-// who adds a -g flag puts
+// who adds a -g flag puts (variance-adjusted: o.flags = C.FF_FLAG_VARIANCE_ADJUSTED, = 4, on UNDIVIDED abundances)
 //	C.ff_options_set_alpha(&o, C.double(*alpha))
 // behind `o.weighted = 1` in the two functions below; C.ff_options_alpha(&o) reads it back (NaN without the flag).
 // alpha = 1 is weighted UniFrac itself, bit for bit; the flag needs `weighted` and excludes -l (FF_FLAG_UNSORTED_WALK).

@@ -19,7 +19,7 @@ SPRSPR_PATH = os.path.join(_HERE, "lib", "sprspr")
 FF_OK = 0
 FF_ERR_ARG, FF_ERR_PARSE, FF_ERR_SPECIES, FF_ERR_DEVICE, FF_ERR_IO, FF_ERR_INTERNAL, FF_ERR_PRECISION = 1, 2, 3, 4, 5, 6, 7
 PRECISION_AUTO, PRECISION_FIXED32, PRECISION_EXACT64 = 0, 1, 2
-PRECISION_FLOAT32 = 3  # reported only: a generalized plan (alpha != 1)
+PRECISION_FLOAT32 = 3  # reported only: a generalized plan (alpha != 1), a variance-adjusted plan
 PRECISION_NAMES = {"auto": 0, "fixed32": 1, "exact64": 2}
 
 
@@ -59,9 +59,10 @@ DISTS_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_int64, POINTER(c_double), c_int64
 TEXT_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_size_t)
 
 KERNEL_NAMES = {0: "pair_sad_kernel", 1: "pair_exact64_kernel", 2: "pair_common_mfma_kernel",
-                3: "pair_sad_sparse_kernel", 4: "pair_common_small_kernel", 5: "pair_exact_unw_kernel", 6: "pair_walk_kernel", 7: "pair_exact64_skip_kernel", 8: "pair_general_kernel"}
+                3: "pair_sad_sparse_kernel", 4: "pair_common_small_kernel", 5: "pair_exact_unw_kernel", 6: "pair_walk_kernel", 7: "pair_exact64_skip_kernel", 8: "pair_general_kernel", 9: "pair_vaw_kernel"}
 FLAG_UNSORTED_WALK = 1
 FLAG_GENERALIZED = 2
+FLAG_VARIANCE_ADJUSTED = 4
 L_REFERENCE = 2
 
 

@@ -19,7 +19,7 @@ from ._lib import FFError, ff_options, ff_plan_info, ff_problem
 
 
 def _opts(weighted: bool, precision="auto", device: int = -1, rank: int = 0, world: int = 1,
-          unsorted_walk: bool = False, alpha: Optional[float] = None) -> ff_options:
+          unsorted_walk: bool = False, alpha: Optional[float] = None, variance_adjusted: bool = False) -> ff_options:
     o = ff_options()
     L.lib().ff_options_default(ctypes.byref(o))
     o.weighted = 1 if weighted else 0
@@ -30,6 +30,8 @@ def _opts(weighted: bool, precision="auto", device: int = -1, rank: int = 0, wor
     o.flags = L.FLAG_UNSORTED_WALK if unsorted_walk else 0
     if alpha is not None:  # generalized UniFrac d(alpha) (FF_FLAG_GENERALIZED); None leaves the options as they are
         L.lib().ff_options_set_alpha(ctypes.byref(o), float(alpha))
+    if variance_adjusted:  # variance-adjusted weighted UniFrac (FF_FLAG_VARIANCE_ADJUSTED): undivided abundances
+        o.flags |= L.FLAG_VARIANCE_ADJUSTED
     return o
 
 
@@ -267,22 +269,24 @@ def flatten_device(tree: Tree, leaf_ptr, leaf_idx, leaf_val, leave_unnormalized:
 
 def unifrac_dists(nodes: FlatNodes, weighted: bool, precision="auto", device: int = -1,
                   rank: int = 0, world: int = 1, out: Optional[np.ndarray] = None, unsorted_walk: bool = False,
-                  alpha: Optional[float] = None) -> np.ndarray:
+                  alpha: Optional[float] = None, variance_adjusted: bool = False) -> np.ndarray:
     """unifracDists (frcfrc/unifrac.go:209): all pair distances of this shard in
     IterPairs order, computed on the GPU.  Returns the full-length array; slots
     outside the shard keep NaN (or the contents of `out`).  alpha (with weighted=True): generalized UniFrac
-    d(alpha), 0 <= alpha <= 1; 1.0 is weighted UniFrac itself, every other value is within 1e-6 absolute."""
+    d(alpha), 0 <= alpha <= 1; 1.0 is weighted UniFrac itself, every other value is within 1e-6 absolute.
+    variance_adjusted (with weighted=True, without alpha): variance-adjusted weighted UniFrac of nodes that carry
+    UNDIVIDED subtree sums (flatten(..., leave_unnormalized=True)), within 1e-6 absolute."""
     n = nodes.n_samples
     if out is None:
         out = np.full(num_pairs(n), np.nan, dtype=np.float64)
-    p, o, err = nodes.problem(), _opts(weighted, precision, device, rank, world, unsorted_walk, alpha), L.errbuf()
+    p, o, err = nodes.problem(), _opts(weighted, precision, device, rank, world, unsorted_walk, alpha, variance_adjusted), L.errbuf()
     L.check(L.lib().ff_unifrac_dists(ctypes.byref(p), ctypes.byref(o), out.ctypes.data, err, L.ERRLEN), err)
     return out
 
 
 def unifrac_text_stream(nodes: FlatNodes, weighted: bool, write, precision="auto", device: int = -1, rank: int = 0,
                         world: int = 1, max_pairs_per_chunk: int = 0, flat_args: bool = False,
-                        unsorted_walk: bool = False, alpha: Optional[float] = None) -> int:
+                        unsorted_walk: bool = False, alpha: Optional[float] = None, variance_adjusted: bool = False) -> int:
     """unifracDists and the loop that prints it (unifrac.go:209-228 + frcfrc.go:58-62) as one lazy sequence of TEXT
     (ff_unifrac_text_stream): `write(bytes)` receives pieces of whole lines, in order, formatted on the device; a
     `write` that returns False stops the computation.  Returns the number of bytes handed over."""
@@ -298,7 +302,7 @@ def unifrac_text_stream(nodes: FlatNodes, weighted: bool, write, precision="auto
             return 0
 
     cb = L.TEXT_FN(on_text)
-    p, o, err = nodes.problem(), _opts(weighted, precision, device, rank, world, unsorted_walk, alpha), L.errbuf()
+    p, o, err = nodes.problem(), _opts(weighted, precision, device, rank, world, unsorted_walk, alpha, variance_adjusted), L.errbuf()
     if flat_args:
         rc = L.lib().ff_unifrac_text_stream_csr(nodes.n_samples, nodes.n_branches, nodes.branch_len.ctypes.data,
                                                 nodes.indptr.ctypes.data, nodes.branch_id.ctypes.data, nodes.abnd.ctypes.data,
@@ -313,7 +317,7 @@ def unifrac_text_stream(nodes: FlatNodes, weighted: bool, write, precision="auto
 
 def unifrac_dists_stream(nodes: FlatNodes, weighted: bool, precision="auto", device: int = -1, rank: int = 0,
                          world: int = 1, max_pairs_per_chunk: int = 0, flat_args: bool = False,
-                         alpha: Optional[float] = None) -> Iterator[Tuple[int, np.ndarray]]:
+                         alpha: Optional[float] = None, variance_adjusted: bool = False) -> Iterator[Tuple[int, np.ndarray]]:
     """unifracDists as the reference has it (frcfrc/unifrac.go:209-228): a lazy, ordered sequence
     that stops computing when the consumer stops.  Yields (slot_begin, distances) pieces of at most
     max_pairs_per_chunk consecutive slots in IterPairs order (ff_unifrac_dists_stream).  Nothing
@@ -345,7 +349,7 @@ def unifrac_dists_stream(nodes: FlatNodes, weighted: bool, precision="auto", dev
         return 0 if state["stop"] else 1
 
     cb = L.DISTS_FN(on_piece)
-    p, o, err = nodes.problem(), _opts(weighted, precision, device, rank, world, alpha=alpha), L.errbuf()
+    p, o, err = nodes.problem(), _opts(weighted, precision, device, rank, world, alpha=alpha, variance_adjusted=variance_adjusted), L.errbuf()
 
     def call():
         try:
@@ -386,10 +390,11 @@ def unifrac_dists_stream(nodes: FlatNodes, weighted: bool, precision="auto", dev
 
 
 def unifrac(table: Table, tree: Tree, weighted: bool, leave_unnormalized: bool = False,
-            precision="auto", device: int = -1, alpha: Optional[float] = None) -> np.ndarray:
-    """unifrac (frcfrc/unifrac.go:97): flatten on the host, distances on the GPU."""
+            precision="auto", device: int = -1, alpha: Optional[float] = None, variance_adjusted: bool = False) -> np.ndarray:
+    """unifrac (frcfrc/unifrac.go:97): flatten on the host, distances on the GPU.  variance_adjusted flattens
+    undivided and sorted whatever leave_unnormalized says."""
     out = np.full(num_pairs(len(table)), np.nan, dtype=np.float64)
-    o, err = _opts(weighted, precision, device, alpha=alpha), L.errbuf()
+    o, err = _opts(weighted, precision, device, alpha=alpha, variance_adjusted=variance_adjusted), L.errbuf()
     L.check(L.lib().ff_unifrac(table._h, tree._h, ctypes.byref(o), _l_mode(leave_unnormalized),
                                out.ctypes.data, err, L.ERRLEN), err)
     return out
@@ -399,9 +404,10 @@ class Plan:
     """Staged inputs resident in HBM + tile schedule (ff_plan)."""
 
     def __init__(self, nodes: Optional[FlatNodes], weighted: bool, precision="auto", device: int = -1,
-                 rank: int = 0, world: int = 1, _handle=None, unsorted_walk: bool = False, alpha: Optional[float] = None):
+                 rank: int = 0, world: int = 1, _handle=None, unsorted_walk: bool = False, alpha: Optional[float] = None,
+                 variance_adjusted: bool = False):
         if _handle is None:
-            p, o, err = nodes.problem(), _opts(weighted, precision, device, rank, world, unsorted_walk, alpha), L.errbuf()
+            p, o, err = nodes.problem(), _opts(weighted, precision, device, rank, world, unsorted_walk, alpha, variance_adjusted), L.errbuf()
             self._h = ctypes.c_void_p()
             L.check(L.lib().ff_plan_create(ctypes.byref(p), ctypes.byref(o), ctypes.byref(self._h), err, L.ERRLEN), err)
         else:
@@ -411,12 +417,13 @@ class Plan:
 
     @classmethod
     def from_leaves(cls, tree: "Tree", leaf_ptr, leaf_idx, leaf_val, weighted: bool, leave_unnormalized: bool = False,
-                    precision="auto", device: int = -1, rank: int = 0, world: int = 1, alpha: Optional[float] = None) -> "Plan":
+                    precision="auto", device: int = -1, rank: int = 0, world: int = 1, alpha: Optional[float] = None,
+                    variance_adjusted: bool = False) -> "Plan":
         """Stage A on the device, then staging (ff_plan_create_from_leaves)."""
         leaf_ptr = np.ascontiguousarray(leaf_ptr, dtype=np.int64)
         leaf_idx = np.ascontiguousarray(leaf_idx, dtype=np.int64)
         leaf_val = np.ascontiguousarray(leaf_val, dtype=np.float64)
-        o, err, h = _opts(weighted, precision, device, rank, world, alpha=alpha), L.errbuf(), ctypes.c_void_p()
+        o, err, h = _opts(weighted, precision, device, rank, world, alpha=alpha, variance_adjusted=variance_adjusted), L.errbuf(), ctypes.c_void_p()
         L.check(L.lib().ff_plan_create_from_leaves(tree._h, len(leaf_ptr) - 1, leaf_ptr.ctypes.data,
                                                    leaf_idx.ctypes.data, leaf_val.ctypes.data,
                                                    _l_mode(leave_unnormalized), ctypes.byref(o),

@@ -6,7 +6,8 @@
 // (frcfrc.go:78-86), the same stderr phase lines and the same output: one
 // distance per line in IterPairs order, formatted like fmt.Fprintln (frcfrc.go:58-62).
 // Errors print "ERROR: <msg>" and exit 2 (common/common.go:13-18).
-// Extensions (not in the reference): -precision auto|fixed32|exact64, -stats, -gpus N, -g ALPHA (generalized UniFrac).
+// Extensions (not in the reference): -precision auto|fixed32|exact64, -stats, -gpus N, -g ALPHA (generalized UniFrac),
+// -vaw (variance-adjusted weighted UniFrac).
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -38,6 +39,7 @@ void usage()
     fputs("  -s\tInput is in sparse format\n", stderr);
     fputs("  -stats\n    \tPrint device statistics to stderr\n", stderr);
     fputs("  -t string\n    \tPath to tree file, required\n", stderr);
+    fputs("  -vaw\n    \tVariance-adjusted weighted UniFrac (Chang et al. 2011) on the undivided abundances; needs -w\n", stderr);
     fputs("  -w\tUse weighted UniFrac (default unweighted)\n", stderr);
 }
 
@@ -49,7 +51,7 @@ int die(const char *msg)
 
 struct Flags {
     std::string in, out, tree, precision = "auto";
-    bool weighted = false, sparse = false, nnorm = false, stats = false, lcompat = false, lsorted = false;
+    bool weighted = false, sparse = false, nnorm = false, stats = false, lcompat = false, lsorted = false, vaw = false;
     long nt = 1, gpus = 1;
     bool nt_given = false;
     double alpha = 1.0;
@@ -98,7 +100,8 @@ int parse_flags(int argc, char **argv, Flags *f)
             return 2;
         }
         bool *bp = name == "w" ? &f->weighted : name == "s" ? &f->sparse : name == "l" ? &f->nnorm
-                   : name == "stats" ? &f->stats : name == "l-compat" ? &f->lcompat : name == "l-sorted" ? &f->lsorted : nullptr;
+                   : name == "stats" ? &f->stats : name == "l-compat" ? &f->lcompat : name == "l-sorted" ? &f->lsorted
+                   : name == "vaw" ? &f->vaw : nullptr;
         if (bp) {
             if (has_value) {
                 if (!parse_bool(value, bp)) {
@@ -200,6 +203,8 @@ extern "C" int ff_frcfrc_main(int argc, char **argv)
     if (f.lsorted && f.lcompat) return die("-l-sorted and -l-compat exclude each other");
     if (f.alpha_given && !f.weighted) return die("-g can only be used with weighted unifrac");
     if (f.alpha_given && !(f.alpha >= 0.0 && f.alpha <= 1.0)) return die(("bad alpha: " + ff::go_v(f.alpha)).c_str());
+    if (f.vaw && !f.weighted) return die("-vaw can only be used with weighted unifrac");
+    if (f.vaw && f.alpha_given) return die("-vaw and -g exclude each other");
     if (f.gpus < 1 || f.gpus > 64) {
         char m[64];
         snprintf(m, sizeof m, "bad number of GPUs: %ld", f.gpus);
@@ -209,6 +214,7 @@ extern "C" int ff_frcfrc_main(int argc, char **argv)
     ff_options_default(&opt);
     opt.weighted = f.weighted;
     if (f.alpha_given) ff_options_set_alpha(&opt, f.alpha);
+    if (f.vaw) opt.flags |= FF_FLAG_VARIANCE_ADJUSTED;  // (the lists are flattened undivided and sorted, with or without -l -l-sorted)
     if (f.precision == "auto") opt.precision = FF_PRECISION_AUTO;
     else if (f.precision == "fixed32") opt.precision = FF_PRECISION_FIXED32;
     else if (f.precision == "exact64") opt.precision = FF_PRECISION_EXACT64;

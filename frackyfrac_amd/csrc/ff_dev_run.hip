@@ -31,6 +31,7 @@ using namespace ff::sched;
 #include "ff_kernels_exact_unw.hpp"
 #include "ff_kernels_exact_w.hpp"
 #include "ff_kernels_general.hpp"
+#include "ff_kernels_vaw.hpp"
 #include "ff_kernels_low.hpp"
 #include "ff_kernels_low_unw.hpp"
 
@@ -309,7 +310,15 @@ int launch_general(ff_plan *pl, hipStream_t st, double *d_out, char *err, size_t
     if (pl->n_xtiles <= 0) return FF_OK;
     if (!g_tile_height_ok(pl->x_tile_h)) return ff::fail(FF_ERR_INTERNAL, err, errlen, "generalized: no kernel for tile height %d", pl->x_tile_h);
     const bool h8 = pl->x_tile_h == 8;
-    auto kern = pl->g_alpha == 0.0   ? (h8 ? pair_general_kernel<G_ZERO, 8> : pair_general_kernel<G_ZERO, 16>)
+    if (pl->vaw) {  // variance-adjusted weighted UniFrac: the same tiles, its own planes
+        auto vkern = h8 ? pair_vaw_kernel<8> : pair_vaw_kernel<16>;
+        vkern<<<dim3((unsigned)((pl->n_xtiles + 3) / 4)), dim3(256), 0, st>>>(pl->d_GT, pl->d_VB, pl->d_VT, inf.ld,
+                                                                            pl->d_len_rows ? pl->d_len_rows : pl->d_len, inf.n_rows, pl->d_xtiles,
+                                                                            pl->n_xtiles, inf.row_begin, inf.row_end, inf.slot_begin, d_out);
+        FF_HIP(hipGetLastError());
+        return FF_OK;
+    }
+    auto kern = pl->g_alpha == 0.0  ? (h8 ? pair_general_kernel<G_ZERO, 8> : pair_general_kernel<G_ZERO, 16>)
                 : pl->g_alpha == 0.5 ? (h8 ? pair_general_kernel<G_HALF, 8> : pair_general_kernel<G_HALF, 16>)
                                      : (h8 ? pair_general_kernel<G_ANY, 8> : pair_general_kernel<G_ANY, 16>);
     kern<<<dim3((unsigned)((pl->n_xtiles + 3) / 4)), dim3(256), 0, st>>>(pl->d_GT, inf.ld, pl->d_len_rows ? pl->d_len_rows : pl->d_len, inf.n_rows,
@@ -398,7 +407,7 @@ int upload_exact64_tiles(ff_plan *pl, int h, char *err, size_t errlen)
     pl->n_xtiles = (int)xt.size();
     pl->x_tile_h = h;
     pl->x_skip = !pl->general && pl->weighted && inf.n_rows > 0 && env_int("FF_X_SKIP", 1) != 0 && (h == 8 || h == 12 || h == 16);
-    inf.kernel = pl->general ? FF_KERNEL_GENERAL_F32 : pl->x_skip ? FF_KERNEL_EXACT_F64_SKIP : FF_KERNEL_EXACT_F64;
+    inf.kernel = pl->vaw ? FF_KERNEL_VAW_F32 : pl->general ? FF_KERNEL_GENERAL_F32 : pl->x_skip ? FF_KERNEL_EXACT_F64_SKIP : FF_KERNEL_EXACT_F64;
     FF_HIP(hipMalloc(&pl->d_xtiles, sizeof(XTile) * std::max<size_t>(xt.size(), 1)));
     if (!xt.empty()) FF_HIP(hipMemcpy(pl->d_xtiles, xt.data(), sizeof(XTile) * xt.size(), hipMemcpyHostToDevice));
     inf.n_wave_slots = (int64_t)xt.size();

@@ -1077,6 +1077,59 @@ int stage_for_general(StageCtx &x, double alpha, char *err, size_t errlen)
     return schedule_exact64(pl, err, errlen);
 }
 
+// Variance-adjusted weighted UniFrac: the two branch-major planes of (x, c) and (p, q) cells, 16 bytes a cell in all,
+// the per-sample (T, 1 / T), and the tiles of pair_vaw_kernel (those of pair_general_kernel).
+int stage_for_vaw(StageCtx &x, char *err, size_t errlen)
+{
+    FF_STAGE_NAMES;
+    pl->general = true;  // (tile heights, schedule and shard re-scheduling of pair_general_kernel)
+    pl->vaw = true;
+    inf.precision = FF_PRECISION_FLOAT32;
+    inf.kernel = FF_KERNEL_VAW_F32;
+    const int64_t ld = round_up(std::max<int64_t>(N, 1), X_TILE_J);
+    inf.ld = ld;
+    inf.rows_padded = R;
+    // (+ G_VALUES_PAD cells: a tile in the last 64 columns reads up to H - 1 row cells, and as many per-sample cells,
+    // past the end)
+    const size_t plane_bytes = sizeof(float2) * ((size_t)std::max<int64_t>(R, 1) * (size_t)ld + G_VALUES_PAD);
+    const size_t vt_bytes = sizeof(float2) * ((size_t)ld + G_VALUES_PAD);
+    inf.staged_bytes = 2.0 * (double)plane_bytes + (double)vt_bytes;
+    FF_ALLOC(pl->d_GT, plane_bytes, "the staged (x, c) plane");
+    FF_ALLOC(pl->d_VB, plane_bytes, "the staged (p, q) plane");
+    FF_ALLOC(pl->d_VT, vt_bytes, "the samples' totals");
+    FF_HIP(hipMemset(pl->d_GT, 0, plane_bytes));
+    FF_HIP(hipMemset(pl->d_VB, 0, plane_bytes));
+    FF_HIP(hipMemset(pl->d_VT, 0, vt_bytes));
+    if (N > 0 && nnz > 0) {
+        Scratch<double> tot;  // T per sample, and behind them the bits of the largest
+        FF_HIP(tot.alloc((size_t)N + 1));
+        FF_HIP(hipMemset(tot.p, 0, sizeof(double) * ((size_t)N + 1)));
+        vaw_totals_kernel<<<dim3((unsigned)N), dim3(256)>>>(d_indptr, d_abnd, tot.p, (unsigned long long *)(tot.p + N));
+        FF_HIP(hipGetLastError());
+        double t_max = 0.0;
+        FF_HIP(hipMemcpy(&t_max, tot.p + N, sizeof t_max, hipMemcpyDeviceToHost));
+        // one power of two for the whole table: the largest total lands in [2^31, 2^32) (ff_kernels_vaw.hpp, "Range")
+        int ex = 0;
+        (void)std::frexp(t_max, &ex);
+        const double scale = t_max > 0.0 ? std::ldexp(1.0, 32 - ex) : 1.0;
+        const int64_t rows_per_block = 64;
+        stage_vaw_fill_kernel<<<dim3((unsigned)((N + 255) / 256), (unsigned)((std::max<int64_t>(R, 1) + rows_per_block - 1) / rows_per_block)),
+                                dim3(256)>>>(tot.p, scale, N, R, rows_per_block, pl->d_GT, pl->d_VT, ld);
+        FF_HIP(hipGetLastError());
+        stage_vaw_kernel<<<dim3((unsigned)N), dim3(256)>>>(d_indptr, d_ids, d_abnd, d_len, tot.p, scale, row_of.p, pl->d_GT, pl->d_VB,
+                                                           pl->d_VT, ld);
+        FF_HIP(hipGetLastError());
+        FF_HIP(hipDeviceSynchronize());  // (tot goes out of scope)
+    }
+    if (row_of.p) {  // treeDists by staged row
+        std::vector<double> lr((size_t)R);
+        for (int64_t r = 0; r < R; ++r) lr[(size_t)r] = c->h_len[(size_t)branch_of_row[(size_t)r]];
+        FF_HIP(hipMalloc(&pl->d_len_rows, sizeof(double) * (size_t)std::max<int64_t>(R, 1)));
+        if (R > 0) FF_HIP(hipMemcpy(pl->d_len_rows, lr.data(), sizeof(double) * (size_t)R, hipMemcpyHostToDevice));
+    }
+    return schedule_exact64(pl, err, errlen);
+}
+
 }  // namespace
 
 // Stages the device-resident flat nodes and builds the schedule.  Takes ownership of *c.
@@ -1133,9 +1186,11 @@ int plan_build(const ff_options *o, DeviceCsr *c, const hipDeviceProp_t &prop, f
 
     // Generalized UniFrac: alpha = 1 is the weighted path itself and goes on below as if the flag were clear; every
     // other alpha ignores `precision` and takes pair_general_kernel.  Nothing to refine or audit: the flat nodes go.
+    // Variance-adjusted weighted UniFrac (FF_FLAG_VARIANCE_ADJUSTED, never with alpha): pair_vaw_kernel, likewise.
     double alpha = 1.0;
-    if (ff::general_alpha(o, &alpha)) {
-        rc = stage_for_general(x, alpha, err, errlen);
+    const bool vaw = (o->flags & FF_FLAG_VARIANCE_ADJUSTED) != 0;
+    if (vaw || ff::general_alpha(o, &alpha)) {
+        rc = vaw ? stage_for_vaw(x, err, errlen) : stage_for_general(x, alpha, err, errlen);
         if (rc) return rc;
         FF_HIP(hipDeviceSynchronize());
         free_and_null(pl->d_indptr);

@@ -123,6 +123,8 @@ void plan_free_device(ff_plan *pl)
     (void)hipFree(pl->d_ptile_ptr);
     (void)hipFree(pl->d_DT);
     (void)hipFree(pl->d_GT);
+    (void)hipFree(pl->d_VB);
+    (void)hipFree(pl->d_VT);
     (void)hipFree(pl->d_len);
     (void)hipFree(pl->d_len_rows);
     (void)hipFree(pl->d_host_out);
@@ -209,8 +211,10 @@ int ff_plan_create(const ff_problem *p, const ff_options *o, ff_plan **plan, cha
         return ff::fail(FF_ERR_ARG, err, errlen, "bad shard %d of %d", o->rank, o->world);
     if (o->precision < FF_PRECISION_AUTO || o->precision > FF_PRECISION_EXACT64)
         return ff::fail(FF_ERR_ARG, err, errlen, "bad precision %d", o->precision);
-    if ((o->flags & ~(FF_FLAG_UNSORTED_WALK | FF_FLAG_GENERALIZED)) != 0) return ff::fail(FF_ERR_ARG, err, errlen, "unknown flags %d", o->flags);
+    if ((o->flags & ~(FF_FLAG_UNSORTED_WALK | FF_FLAG_GENERALIZED | FF_FLAG_VARIANCE_ADJUSTED)) != 0)
+        return ff::fail(FF_ERR_ARG, err, errlen, "unknown flags %d", o->flags);
     int rc = ff::check_alpha(o, err, errlen);
+    if (rc == FF_OK) rc = ff::check_vaw(o, err, errlen);
     if (rc) return rc;
     rc = validate_problem(p, err, errlen, (o->flags & FF_FLAG_UNSORTED_WALK) != 0);
     if (rc) return rc;
@@ -674,6 +678,9 @@ int ff_plan_create_from_leaves(const ff_tree *tree, int64_t n_samples, const int
     }
     {
         int rc = ff::check_alpha(o, err, errlen);
+        if (rc == FF_OK) rc = ff::check_vaw(o, err, errlen);
+        // (variance adjusted is defined on undivided, sorted lists: that is what gets flattened)
+        if (o->flags & FF_FLAG_VARIANCE_ADJUSTED) leave_unnormalized = 1;
         if (rc == FF_OK) rc = ff::check_general_values(o, tree->dist.data(), B, "branch length", err, errlen);
         if (rc == FF_OK) rc = ff::check_general_values(o, leaf_val, leaf_ptr[n_samples], "leaf value", err, errlen);
         if (rc) return rc;

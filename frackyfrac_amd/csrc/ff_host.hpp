@@ -29,6 +29,9 @@ int fail(int code, char *err, size_t errlen, const char *fmt, ...)
 int check_alpha(const ff_options *o, char *err, size_t errlen);
 bool general_alpha(const ff_options *o, double *alpha);
 int check_general_values(const ff_options *o, const double *v, int64_t n, const char *what, char *err, size_t errlen);
+// Variance-adjusted weighted UniFrac (FF_FLAG_VARIANCE_ADJUSTED; a no-op without the flag): weighted, AUTO, and neither
+// alpha nor the unsorted walk.  (check_general_values looks at the values under this flag too.)
+int check_vaw(const ff_options *o, char *err, size_t errlen);
 
 // Go's %q for a string, Go's %v for a float64, Go's %f for a float64.
 std::string go_quote(const std::string &s);

@@ -102,6 +102,73 @@ __global__ void stage_general_kernel(const int64_t *__restrict__ indptr, const i
     }
 }
 
+// Stage variance-adjusted weighted UniFrac (pair_vaw_kernel, ff_kernels_vaw.hpp), three kernels.
+// (1) vaw_totals_kernel, a block per sample: T_s = the largest abundance of the list (the root's subtree sum; 0 for an
+// empty sample), and the largest T of the table (non-negative binary64 numbers order as their bits do).
+__global__ __launch_bounds__(256)
+void vaw_totals_kernel(const int64_t *__restrict__ indptr, const double *__restrict__ abnd, double *__restrict__ T,
+                       unsigned long long *__restrict__ t_max)
+{
+    __shared__ double part[256];
+    const int64_t s = blockIdx.x;
+    double m = 0.0;
+    for (int64_t t = indptr[s] + threadIdx.x; t < indptr[s + 1]; t += blockDim.x) m = fmax(m, abnd[t]);
+    part[threadIdx.x] = m;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] = fmax(part[threadIdx.x], part[threadIdx.x + w]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        T[s] = part[0];
+        atomicMax(t_max, (unsigned long long)__double_as_longlong(part[0]));
+    }
+}
+
+// A non-zero staged abundance, scaled, as a NORMAL binary32 number that leaves the product m r room (2^-60 at least).
+__device__ __forceinline__ double vaw_floor(double v) { return v > 0.0 ? fmax(v, 0x1p-60) : 0.0; }
+
+// (2) stage_vaw_fill_kernel, grid (columns / 256, row chunks): per sample (T, 1 / T), scaled by `scale` (one power of
+// two for the whole table), and c = T in EVERY cell of the sample's column of plane A -- what c is where the sample
+// has not the branch.  The columns behind the last sample and plane B stay zero.
+__global__ void stage_vaw_fill_kernel(const double *__restrict__ T, double scale, int64_t n_samples, int64_t rows,
+                                      int64_t rows_per_block, float2 *__restrict__ VA, float2 *__restrict__ VT, int64_t ld)
+{
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_samples) return;
+    const double t = vaw_floor(T[s] * scale);
+    const float2 cell = make_float2(0.0f, (float)t);
+    if (blockIdx.y == 0) VT[s] = make_float2((float)t, t > 0.0 ? (float)(1.0 / t) : 0.0f);
+    const int64_t r0 = (int64_t)blockIdx.y * rows_per_block, r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
+    for (int64_t r = r0; r < r1; ++r) VA[r * ld + s] = cell;
+}
+
+// (3) stage_vaw_kernel, a block per sample: per flat node the cells (x, c) and (p, q).  x, c = T - x (exactly 0 where
+// x == T) and q = l (x / T) / sqrt(x) -- the column's part of a term in which only this sample has the branch -- are
+// evaluated in binary64 and rounded once; p is the BINARY32 product x (1 / T) of the staged numbers, the operation by
+// which the kernel forms the p of its rows: equal lists give equal bits on both sides of a pair.
+__global__ void stage_vaw_kernel(const int64_t *__restrict__ indptr, const int32_t *__restrict__ branch_id,
+                                 const double *__restrict__ abnd, const double *__restrict__ branch_len,
+                                 const double *__restrict__ T, double scale, const int32_t *__restrict__ row_of,
+                                 float2 *__restrict__ VA, float2 *__restrict__ VB, const float2 *__restrict__ VT, int64_t ld)
+{
+    const int64_t s = blockIdx.x;
+    const int64_t b0 = indptr[s], b1 = indptr[s + 1];
+    const double tot = T[s];
+    const float inv_t = VT[s].y;
+    for (int64_t t = b0 + threadIdx.x; t < b1; t += blockDim.x) {
+        const int32_t b = branch_id[t];
+        const double x = abnd[t], l = branch_len[b];
+        if (!(x > 0.0)) continue;  // (a flat node without abundance: the sample has not the branch)
+        const double xs = vaw_floor(x * scale);
+        const float xf = (float)xs;
+        const double q = l * (x / tot) / sqrt(xs);
+        const int64_t at = (int64_t)(row_of ? row_of[b] : b) * ld + s;
+        VA[at] = make_float2(xf, (float)vaw_floor((tot - x) * scale));
+        VB[at] = make_float2(__fmul_rn(xf, inv_t), q > 0.0 ? fmaxf((float)q, 1.17549435e-38f) : 0.0f);
+    }
+}
+
 // W_s = sum_b q_s(b): grid (ld/64, row chunks), one column per lane.
 __global__ void colsum_kernel(const uint32_t *__restrict__ QT, int64_t ld, int64_t rows,
                               int64_t rows_per_block, unsigned long long *__restrict__ W)

@@ -51,10 +51,23 @@ bool general_alpha(const ff_options *o, double *alpha)
 
 int check_general_values(const ff_options *o, const double *v, int64_t n, const char *what, char *err, size_t errlen)
 {
-    if (!(o->flags & FF_FLAG_GENERALIZED)) return FF_OK;
+    if (!(o->flags & (FF_FLAG_GENERALIZED | FF_FLAG_VARIANCE_ADJUSTED))) return FF_OK;
+    const char *opt = (o->flags & FF_FLAG_GENERALIZED) ? "alpha" : "variance adjusted";
     for (int64_t k = 0; k < n; ++k)
         if (!(v[k] >= 0.0) || !std::isfinite(v[k]))
-            return fail(FF_ERR_ARG, err, errlen, "alpha: %s %lld is negative or not finite (%s)", what, (long long)k, go_v(v[k]).c_str());
+            return fail(FF_ERR_ARG, err, errlen, "%s: %s %lld is negative or not finite (%s)", opt, what, (long long)k, go_v(v[k]).c_str());
+    return FF_OK;
+}
+
+int check_vaw(const ff_options *o, char *err, size_t errlen)
+{
+    if (!(o->flags & FF_FLAG_VARIANCE_ADJUSTED)) return FF_OK;
+    if (!o->weighted) return fail(FF_ERR_ARG, err, errlen, "variance adjusted can only be used with weighted unifrac");
+    if (o->flags & FF_FLAG_GENERALIZED) return fail(FF_ERR_ARG, err, errlen, "variance adjusted cannot be used with alpha");
+    if (o->flags & FF_FLAG_UNSORTED_WALK)
+        return fail(FF_ERR_ARG, err, errlen, "variance adjusted cannot be used with the unsorted walk (FF_FLAG_UNSORTED_WALK, FF_L_REFERENCE)");
+    if (o->precision != FF_PRECISION_AUTO)
+        return fail(FF_ERR_ARG, err, errlen, "variance adjusted takes the precision auto only (it runs binary32 terms, binary64 sums)");
     return FF_OK;
 }
 

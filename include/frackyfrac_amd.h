@@ -97,7 +97,7 @@ typedef enum ff_precision {
                                  table the unweighted kernel runs only the branches some sample
                                  of a pair tile has (ff_plan_info.active_fraction; same bits) */
     FF_PRECISION_FLOAT32 = 3  /* REPORTED ONLY (ff_plan_info.precision of a generalized plan, FF_FLAG_GENERALIZED
-                                 with alpha != 1): binary32 terms summed in binary64, within 1e-6 ABSOLUTE of
+                                 with alpha != 1, and of a FF_FLAG_VARIANCE_ADJUSTED plan): binary32 terms summed in binary64, within 1e-6 ABSOLUTE of
                                  d(alpha).  As a requested precision it is refused ("bad precision")          */
 } ff_precision;
 
@@ -135,6 +135,24 @@ typedef struct ff_options {
  * FF_L_REFERENCE) with it; a branch length or an abundance that is negative or not finite (the bound needs
  * non-negative terms). */
 #define FF_FLAG_GENERALIZED 2
+/* FF_FLAG_VARIANCE_ADJUSTED: variance-adjusted weighted UniFrac, "VAW" (Chang, Luan & Sun 2011; `variance_adjust`
+ * in Striped UniFrac).  No payload: reserved[] stays 0.  The flat-node abundances are UNDIVIDED subtree sums x_s(b)
+ * ("counts": any non-negative finite numbers; the sorted -l form).  Per sample T_s = the largest abundance of its
+ * list (the root's subtree sum; 0 for an empty sample), p_s(b) = x_s(b) / T_s, c_s(b) = T_s - x_s(b) (T_s where
+ * the sample has not the branch).  Per pair, with m_b = x_i(b) + x_j(b) and r_b = c_i(b) + c_j(b), over the branches
+ * with m_b r_b > 0 ONLY (neither sample has the branch, or it holds everything of both: dropped):
+ *     d_VAW = sum_b l_b |p_i(b) - p_j(b)| / sqrt(m_b r_b)  /  sum_b l_b (p_i(b) + p_j(b)) / sqrt(m_b r_b)     (0 / 0 = NaN)
+ * This is the paper's normalisation -- p = x / T, true proportions --, deliberately NOT a re-weighting of the
+ * divisor of the reference's normalizeFlatNodes.  Identical samples give 0; an empty sample against another 1 where
+ * a term survives and NaN otherwise; two samples wholly under the same single leaf NaN.
+ * The entry points that flatten (ff_unifrac, ff_plan_create_from_leaves, frcfrc -w -vaw) flatten undivided and
+ * sorted under this flag whatever `leave_unnormalized` says.  The plan runs pair_vaw_kernel (FF_KERNEL_VAW_F32,
+ * reported precision FF_PRECISION_FLOAT32): binary32 terms, binary64 sums, within 1e-6 ABSOLUTE of the formula; a
+ * pair's value does not depend on tile height, shard or launch; nothing to refine or audit.
+ * FF_ERR_ARG, before the device is touched: weighted == 0; FF_FLAG_GENERALIZED, FF_FLAG_UNSORTED_WALK or
+ * FF_L_REFERENCE with it; a precision other than FF_PRECISION_AUTO; a branch length or an abundance that is
+ * negative or not finite. */
+#define FF_FLAG_VARIANCE_ADJUSTED 4
 
 /* Fills *o with the defaults: unweighted, AUTO, current device, rank 0 of 1. */
 void ff_options_default(ff_options *o);
@@ -283,9 +301,13 @@ typedef enum ff_kernel {
     FF_KERNEL_EXACT_F64_SKIP = 7, /* pair_exact64_skip_kernel: EXACT64 weighted; a branch a row has not adds
                                      l * y twice (unifrac.go:186-187) instead of the six operations of
                                      :191-192 on a zero -- same bits as FF_KERNEL_EXACT_F64               */
-    FF_KERNEL_GENERAL_F32 = 8     /* pair_general_kernel: generalized UniFrac d(alpha), alpha != 1
+    FF_KERNEL_GENERAL_F32 = 8,    /* pair_general_kernel: generalized UniFrac d(alpha), alpha != 1
                                      (FF_FLAG_GENERALIZED): a branch a row has not adds the column's own term
                                      l y^alpha to both sums, one where both have it costs one power         */
+    FF_KERNEL_VAW_F32 = 9         /* pair_vaw_kernel: variance-adjusted weighted UniFrac
+                                     (FF_FLAG_VARIANCE_ADJUSTED): one reciprocal square root per term with at
+                                     least one side present, the column's staged part times it where the row
+                                     has not the branch                                                     */
 } ff_kernel;
 
 /* Stage: quantise / densify the flat nodes into the branch-major matrix in HBM
