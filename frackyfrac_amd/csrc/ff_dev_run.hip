@@ -34,6 +34,7 @@ using namespace ff::sched;
 #include "ff_kernels_vaw.hpp"
 #include "ff_kernels_low.hpp"
 #include "ff_kernels_low_unw.hpp"
+#include "ff_kernels_low_general.hpp"
 
 }  // namespace
 
@@ -48,23 +49,29 @@ using namespace ff::sched;
 
 namespace {
 
-// A split plan's blocks of pairs (pair_low_kernel, pair_low_unw_kernel) that hold a row of the shard -- sample blocks
-// bi x bj <= bi -- and the shard's slots of their sums.
+// A split plan's blocks of pairs (pair_low_kernel, pair_low_unw_kernel, pair_low_general_kernel) that hold a row of the
+// shard -- sample blocks bi x bj <= bi -- and the shard's slots of their sums.  A generalized plan's diagonal blocks
+// come first (a launch of their own), and its sums are the pairs' (Mn, Md), 16 bytes a slot, in d_glow.
 int schedule_low_tiles(ff_plan *pl, char *err, size_t errlen)
 {
     const ff_plan_info &inf = pl->info;
     const int64_t N = inf.n_samples, n_slots = inf.slot_end - inf.slot_begin;
     free_and_null(pl->d_low_tiles);
     free_and_null(pl->d_mlow);
-    pl->n_low_tiles = 0;
+    free_and_null(pl->d_glow);
+    pl->n_low_tiles = pl->n_low_diag = 0;
     if (!pl->split || n_slots <= 0) return FF_OK;
     std::vector<LowTile> lt;
+    if (pl->general)
+        for (int64_t bi = inf.row_begin / pl->low_tile; bi * pl->low_tile < std::min(inf.row_end, N); ++bi) lt.push_back({(int32_t)bi, (int32_t)bi});
+    pl->n_low_diag = (int)lt.size();
     for (int64_t bi = inf.row_begin / pl->low_tile; bi * pl->low_tile < std::min(inf.row_end, N); ++bi)
-        for (int64_t bj = 0; bj <= bi; ++bj) lt.push_back({(int32_t)bi, (int32_t)bj});
+        for (int64_t bj = 0; bj + (pl->general ? 1 : 0) <= bi; ++bj) lt.push_back({(int32_t)bi, (int32_t)bj});
     pl->n_low_tiles = (int)lt.size();
     FF_HIP(hipMalloc(&pl->d_low_tiles, sizeof(LowTile) * std::max<size_t>(lt.size(), 1)));
     if (!lt.empty()) FF_HIP(hipMemcpy(pl->d_low_tiles, lt.data(), sizeof(LowTile) * lt.size(), hipMemcpyHostToDevice));
-    FF_ALLOC(pl->d_mlow, sizeof(uint32_t) * (size_t)n_slots, "the rare rows' sums");
+    if (pl->general) FF_ALLOC(pl->d_glow, sizeof(ulong2) * (size_t)n_slots, "the rare rows' sums");
+    else FF_ALLOC(pl->d_mlow, sizeof(uint32_t) * (size_t)n_slots, "the rare rows' sums");
     return FF_OK;
 }
 
@@ -304,7 +311,7 @@ int refine_blocks_per_cu()
 }
 
 // One launch of pair_general_kernel: the form of t = s^(alpha - 1) and the tile height are template parameters.
-int launch_general(ff_plan *pl, hipStream_t st, double *d_out, char *err, size_t errlen)
+int launch_general(ff_plan *pl, hipStream_t st, double *d_out, hipEvent_t ev_mid, char *err, size_t errlen)
 {
     const ff_plan_info &inf = pl->info;
     if (pl->n_xtiles <= 0) return FF_OK;
@@ -318,21 +325,53 @@ int launch_general(ff_plan *pl, hipStream_t st, double *d_out, char *err, size_t
         FF_HIP(hipGetLastError());
         return FF_OK;
     }
+    const float am1 = (float)(pl->g_alpha - 1.0);
+    if (pl->split) {
+        // The rare rows first (inside the timed region; the parts event stands behind them): pair_low_general_kernel over
+        // the diagonal blocks of pairs, then over the others, leaves (Mn, Md) in d_glow; the matrix rows' kernel -- its
+        // SPLIT instantiation, over the rows left in d_GT -- adds PR_i + PR_j - M in its epilogue.
+        const int n_diag = pl->n_low_diag, n_off = pl->n_low_tiles - pl->n_low_diag;
+#define FF_LG_LAUNCH(KIND)                                                                                                  \
+    do {                                                                                                                    \
+        if (n_diag > 0)                                                                                                     \
+            pair_low_general_kernel<KIND, true><<<dim3((unsigned)n_diag), dim3(LOW_G_THREADS), 0, st>>>(                      \
+                pl->d_low_ptr, pl->d_low_entg, pl->d_low_len, pl->d_low_bits, pl->low_words, pl->low_rows + 1, pl->d_low_tiles, \
+                inf.n_samples, inf.row_begin, inf.row_end, inf.slot_begin, pl->g_e, am1, pl->d_glow);                         \
+        if (n_off > 0)                                                                                                      \
+            pair_low_general_kernel<KIND, false><<<dim3((unsigned)n_off), dim3(LOW_G_THREADS), 0, st>>>(                      \
+                pl->d_low_ptr, pl->d_low_entg, pl->d_low_len, pl->d_low_bits, pl->low_words, pl->low_rows + 1,                \
+                pl->d_low_tiles + n_diag, inf.n_samples, inf.row_begin, inf.row_end, inf.slot_begin, pl->g_e, am1, pl->d_glow); \
+    } while (0)
+        if (pl->g_alpha == 0.0) FF_LG_LAUNCH(G_ZERO);
+        else if (pl->g_alpha == 0.5) FF_LG_LAUNCH(G_HALF);
+        else FF_LG_LAUNCH(G_ANY);
+#undef FF_LG_LAUNCH
+        FF_HIP(hipGetLastError());
+        if (ev_mid) FF_HIP(hipEventRecord(ev_mid, st));
+        auto skern = pl->g_alpha == 0.0  ? (h8 ? pair_general_kernel<G_ZERO, 8, true> : pair_general_kernel<G_ZERO, 16, true>)
+                     : pl->g_alpha == 0.5 ? (h8 ? pair_general_kernel<G_HALF, 8, true> : pair_general_kernel<G_HALF, 16, true>)
+                                          : (h8 ? pair_general_kernel<G_ANY, 8, true> : pair_general_kernel<G_ANY, 16, true>);
+        skern<<<dim3((unsigned)((pl->n_xtiles + 3) / 4)), dim3(256), 0, st>>>(pl->d_GT, inf.ld, pl->d_len_rows, inf.n_rows - pl->low_rows, am1,
+                                                                            pl->d_xtiles, pl->n_xtiles, inf.row_begin, inf.row_end,
+                                                                            inf.slot_begin, d_out, pl->d_glow, pl->d_PR, std::ldexp(1.0, -pl->g_e));
+        FF_HIP(hipGetLastError());
+        return FF_OK;
+    }
     auto kern = pl->g_alpha == 0.0  ? (h8 ? pair_general_kernel<G_ZERO, 8> : pair_general_kernel<G_ZERO, 16>)
                 : pl->g_alpha == 0.5 ? (h8 ? pair_general_kernel<G_HALF, 8> : pair_general_kernel<G_HALF, 16>)
                                      : (h8 ? pair_general_kernel<G_ANY, 8> : pair_general_kernel<G_ANY, 16>);
     kern<<<dim3((unsigned)((pl->n_xtiles + 3) / 4)), dim3(256), 0, st>>>(pl->d_GT, inf.ld, pl->d_len_rows ? pl->d_len_rows : pl->d_len, inf.n_rows,
-                                                                       (float)(pl->g_alpha - 1.0), pl->d_xtiles, pl->n_xtiles, inf.row_begin,
-                                                                       inf.row_end, inf.slot_begin, d_out);
+                                                                       am1, pl->d_xtiles, pl->n_xtiles, inf.row_begin,
+                                                                       inf.row_end, inf.slot_begin, d_out, nullptr, nullptr, 0.0);
     FF_HIP(hipGetLastError());
     return FF_OK;
 }
 
 // One launch of the EXACT64 pair kernel with the plan's tile height.
-int launch_exact64(ff_plan *pl, hipStream_t st, double *d_out, char *err, size_t errlen)
+int launch_exact64(ff_plan *pl, hipStream_t st, double *d_out, hipEvent_t ev_mid, char *err, size_t errlen)
 {
     const ff_plan_info &inf = pl->info;
-    if (pl->general) return launch_general(pl, st, d_out, err, errlen);
+    if (pl->general) return launch_general(pl, st, d_out, ev_mid, err, errlen);
     if (pl->xu) {
         if (pl->n_xutiles > 0 && pl->xu_skip)
             pair_exact_unw_skip_kernel<<<dim3((unsigned)pl->n_xutiles), dim3(64), 0, st>>>(pl->d_Xbits, pl->xu_ldx, pl->d_xu_len_words,
@@ -479,6 +518,10 @@ int schedule_exact64(ff_plan *pl, char *err, size_t errlen)
 {
     ff_plan_info &inf = pl->info;
     if (pl->xu) return schedule_exact_unw(pl, err, errlen);
+    if (pl->general) {  // (a generalized plan's rare rows: the shard's blocks of pairs and d_glow)
+        const int rc = schedule_low_tiles(pl, err, errlen);
+        if (rc != FF_OK) return rc;
+    }
     if (pl->x_tile_h == 0) {
         const int forced = env_int("FF_X_TILE_H", 0);
         int h = X_TILE_H_DEFAULT;
@@ -743,7 +786,7 @@ int plan_run_impl(ff_plan *pl, hipStream_t st, double *d_out, bool timed, char *
     } else {
         if (timed) FF_HIP(hipEventRecord(ev0, st));
         {
-            const int rc = launch_exact64(pl, st, d_out, err, errlen);
+            const int rc = launch_exact64(pl, st, d_out, timed ? ev_mid : nullptr, err, errlen);
             if (rc != FF_OK) return rc;
         }
         if (timed) FF_HIP(hipEventRecord(ev1, st));

@@ -409,7 +409,9 @@ int compact_branches(StageCtx &x, char *err, size_t errlen)
 
 // The rare rows of a split plan (pl->split, low_tile, low_rows are set; low_of: branch id -> rare row or -1) grouped by
 // sample block: counts -> positions -> entries -> row bitmaps.  Weighted: (sample, value) pairs at the scale e for
-// pair_low_kernel; unweighted: the samples' 16-bit places alone for pair_low_unw_kernel (k by rare row is the caller's).
+// pair_low_kernel; unweighted: the samples' 16-bit places alone for pair_low_unw_kernel (k by rare row is the caller's);
+// generalized (pl->general): (place, x, gfix(p, e)) for pair_low_general_kernel, and the samples' sums of gfix(p) in d_PR
+// (the lengths by rare row are the caller's).
 int build_low_index(StageCtx &x, const int32_t *low_of, int64_t Rl, int e, char *err, size_t errlen)
 {
     FF_STAGE_NAMES;
@@ -441,7 +443,14 @@ int build_low_index(StageCtx &x, const int32_t *low_of, int64_t Rl, int e, char 
     const uint32_t n_entries = (uint32_t)run;
     FF_HIP(hipMemcpy(totals.p, h_base.data(), sizeof(uint32_t) * (size_t)nb, hipMemcpyHostToDevice));
     low_add_base_kernel<<<dim3((unsigned)((cells + 255) / 256)), dim3(256)>>>(pl->d_low_ptr, rows1, nb, totals.p);
-    if (weighted) {
+    if (pl->general) {
+        FF_ALLOC(pl->d_low_entg, sizeof(LowGEntry) * (size_t)low_g_alloc_entries(n_entries), "the rare rows' entries");
+        FF_HIP(hipMemset(pl->d_low_entg + n_entries, 0, sizeof(LowGEntry) * LOW_G_SPARE));  // (spare: ff_schedule.hpp)
+        FF_HIP(hipMalloc(&pl->d_PR, sizeof(unsigned long long) * (size_t)inf.ld));
+        FF_HIP(hipMemset(pl->d_PR, 0, sizeof(unsigned long long) * (size_t)inf.ld));
+        low_fill_general_kernel<<<dim3((unsigned)N), dim3(256)>>>(d_indptr, d_ids, d_abnd, d_len, pl->g_alpha, e, low_of, rows1, pl->low_tile,
+                                                                   pl->d_low_ptr, cursor.p, pl->d_low_entg, pl->d_PR);
+    } else if (weighted) {
         FF_ALLOC(pl->d_low_ent, sizeof(uint2) * ((size_t)n_entries + 4), "the rare rows' entries");
         FF_HIP(hipMemset(pl->d_low_ent + n_entries, 0, sizeof(uint2) * 4));  // (spare: pair_low_kernel loads four at a time, and adds the zeros)
         low_fill_kernel<<<dim3((unsigned)N), dim3(256)>>>(d_indptr, d_ids, d_abnd, d_len, e, low_of, rows1, pl->low_tile, pl->d_low_ptr, cursor.p,
@@ -455,7 +464,7 @@ int build_low_index(StageCtx &x, const int32_t *low_of, int64_t Rl, int e, char 
     low_bits_kernel<<<dim3((unsigned)pl->low_words, (unsigned)nb), dim3(64)>>>(pl->d_low_ptr, Rl, rows1, pl->low_words, pl->d_low_bits);
     FF_HIP(hipGetLastError());
     FF_HIP(hipDeviceSynchronize());  // (the scratch arrays go out of scope)
-    inf.staged_bytes += 4.0 * (double)cells + (weighted ? 8.0 : 2.0) * (double)n_entries + 8.0 * (double)nb * (double)pl->low_words;
+    inf.staged_bytes += 4.0 * (double)cells + (pl->general ? 16.0 : weighted ? 8.0 : 2.0) * (double)n_entries + 8.0 * (double)nb * (double)pl->low_words;
     return FF_OK;
 }
 
@@ -1060,15 +1069,100 @@ int stage_for_general(StageCtx &x, double alpha, char *err, size_t errlen)
     const int64_t ld = round_up(std::max<int64_t>(N, 1), X_TILE_J);
     inf.ld = ld;
     inf.rows_padded = R;
+    // Sparse tables: the rows few samples reach leave the matrix (ff_kernels_low_general.hpp).  The matrix
+    // kernel walks every staged row of every pair tile; a rare row r with n_r flat nodes costs pair_low_general_kernel
+    // n_r^2 / 2 updates whatever the number of pairs.  FF_SPARSE_SPLIT = 1 takes every row of up to N / LOW_SHARE_DIV
+    // samples out of the matrix, 0 or unset keeps them all: the kernel's cost per visit and per update has not been
+    // measured against the matrix kernel's per row and tile yet, and without those constants there is no estimate to
+    // follow (DESIGN 4.10's lesson: not borrowed from another kernel).  Forced or not, the split is DECLINED where the
+    // truncation of gfix could show: 2 (rare rows) 2^-e > 2^-26 (the smallest non-empty sample's total of terms).
+    Scratch<int32_t> mat_of, low_of;  // branch id -> row of the matrix / rare row (-1: not there)
+    std::vector<int32_t> h_mat, h_low;
+    int64_t Rm = R, Rl = 0;
+    if (env_int("FF_SPARSE_SPLIT", -1) > 0 && N >= 2 && nnz > 0 && R > 0) {
+        Scratch<int32_t> cnt;
+        Scratch<double> tot;
+        FF_HIP(cnt.alloc((size_t)R));
+        FF_HIP(tot.alloc((size_t)N));
+        FF_HIP(hipMemset(cnt.p, 0, sizeof(int32_t) * (size_t)R));
+        row_counts_kernel<<<dim3((unsigned)std::min<int64_t>((nnz + 255) / 256, 1 << 16)), dim3(256)>>>(d_ids, nnz, row_of.p, cnt.p);
+        general_totals_kernel<<<dim3((unsigned)N), dim3(256)>>>(d_indptr, d_ids, d_abnd, d_len, alpha, tot.p);
+        FF_HIP(hipGetLastError());
+        std::vector<int32_t> h_cnt((size_t)R);
+        std::vector<double> h_tot((size_t)N);
+        FF_HIP(hipMemcpy(h_cnt.data(), cnt.p, sizeof(int32_t) * (size_t)R, hipMemcpyDeviceToHost));
+        FF_HIP(hipMemcpy(h_tot.data(), tot.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
+        double t_max = 0.0, t_min = INFINITY;  // (over the samples that have anything)
+        for (const double t : h_tot) {
+            t_max = std::max(t_max, t);
+            if (t > 0.0) t_min = std::min(t_min, t);
+        }
+        const int64_t cap = N / LOW_SHARE_DIV;
+        std::vector<int64_t> rare;
+        double rare_entries = 0, upd = 0;
+        for (int64_t r = 0; r < R; ++r)
+            if (h_cnt[(size_t)r] <= cap) {
+                rare.push_back(r);
+                rare_entries += (double)h_cnt[(size_t)r];
+                upd += 0.5 * (double)h_cnt[(size_t)r] * (double)(h_cnt[(size_t)r] - 1);
+            }
+        int ex = 0;
+        (void)std::frexp(t_max, &ex);  // t_max in [2^(ex - 1), 2^ex)
+        const int e = G_FIX_TOP + 1 - ex;
+        const int64_t nblk = (N + LOW_G_TILE - 1) / LOW_G_TILE;
+        // (the index is (rare rows + 1) x sample blocks words, twice while it is built: not beyond 4 GB; and it counts
+        // the rare rows' entries in 32 bits)
+        const bool fits = 8.0 * (double)(rare.size() + 1) * (double)nblk <= 4e9 && rare_entries < 4.0e9;
+        const bool exact_enough = std::isfinite(t_max) && t_max > 0.0 &&
+                                  2.0 * (double)rare.size() * std::ldexp(1.0, -e) <= std::ldexp(t_min, -26);
+        if (!rare.empty() && fits && exact_enough) {
+            // numbered by DESCENDING sample count, as the other paths' rare rows are; the matrix rows keep the staged order
+            std::stable_sort(rare.begin(), rare.end(), [&](int64_t u, int64_t v) { return h_cnt[(size_t)u] > h_cnt[(size_t)v]; });
+            h_mat.assign((size_t)B, -1);
+            h_low.assign((size_t)B, -1);
+            for (int64_t r : rare) h_low[(size_t)(branch_of_row.empty() ? r : branch_of_row[(size_t)r])] = (int32_t)Rl++;
+            Rm = 0;
+            for (int64_t r = 0; r < R; ++r) {
+                const int64_t b = branch_of_row.empty() ? r : branch_of_row[(size_t)r];
+                if (h_low[(size_t)b] < 0) h_mat[(size_t)b] = (int32_t)Rm++;
+            }
+            FF_HIP(mat_of.alloc((size_t)B));
+            FF_HIP(low_of.alloc((size_t)B));
+            FF_HIP(hipMemcpy(mat_of.p, h_mat.data(), sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice));
+            FF_HIP(hipMemcpy(low_of.p, h_low.data(), sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice));
+            pl->split = true;
+            pl->low_tile = LOW_G_TILE;
+            pl->low_rows = Rl;
+            pl->g_e = e;
+            inf.rare_rows = Rl;
+            // (the kernel's own work, updates of a pair's two sums; the shard's share of them: its pairs of all)
+            inf.rare_updates = upd * std::max(1.0, (double)n_slots) / std::max(1.0, 0.5 * (double)N * (double)(N - 1));
+        }
+    }
     // (+ G_VALUES_PAD cells: a tile in the last 64 columns reads up to H - 1 cells past the last row's end)
-    const size_t gt_bytes = sizeof(float2) * ((size_t)std::max<int64_t>(R, 1) * (size_t)ld + G_VALUES_PAD);
+    const size_t gt_bytes = sizeof(float2) * ((size_t)std::max<int64_t>(Rm, 1) * (size_t)ld + G_VALUES_PAD);
     inf.staged_bytes = (double)gt_bytes;
     FF_ALLOC(pl->d_GT, gt_bytes, "the staged (x, l x^alpha) matrix");
     FF_HIP(hipMemset(pl->d_GT, 0, gt_bytes));
     if (N > 0 && nnz > 0)
-        stage_general_kernel<<<dim3((unsigned)N), dim3(256)>>>(d_indptr, d_ids, d_abnd, d_len, alpha, row_of.p, pl->d_GT, ld);
+        stage_general_kernel<<<dim3((unsigned)N), dim3(256)>>>(d_indptr, d_ids, d_abnd, d_len, alpha, pl->split ? mat_of.p : row_of.p,
+                                                                pl->d_GT, ld);
     FF_HIP(hipGetLastError());
-    if (row_of.p) {  // treeDists by staged row
+    if (pl->split) {  // treeDists by matrix row (binary64), and by rare row as the kernels use them (binary32)
+        std::vector<double> lr((size_t)std::max<int64_t>(Rm, 1), 0.0);
+        std::vector<float> ll((size_t)Rl);
+        for (int64_t b = 0; b < B; ++b) {
+            if (h_mat[(size_t)b] >= 0) lr[(size_t)h_mat[(size_t)b]] = c->h_len[(size_t)b];
+            if (h_low[(size_t)b] >= 0) ll[(size_t)h_low[(size_t)b]] = (float)c->h_len[(size_t)b];
+        }
+        FF_HIP(hipMalloc(&pl->d_len_rows, sizeof(double) * lr.size()));
+        FF_HIP(hipMemcpy(pl->d_len_rows, lr.data(), sizeof(double) * lr.size(), hipMemcpyHostToDevice));
+        FF_HIP(hipMalloc(&pl->d_low_len, sizeof(float) * ll.size()));
+        FF_HIP(hipMemcpy(pl->d_low_len, ll.data(), sizeof(float) * ll.size(), hipMemcpyHostToDevice));
+        inf.staged_bytes += 4.0 * (double)Rl + 8.0 * (double)ld;
+        const int rc = build_low_index(x, low_of.p, Rl, pl->g_e, err, errlen);
+        if (rc != FF_OK) return rc;
+    } else if (row_of.p) {  // treeDists by staged row
         std::vector<double> lr((size_t)R);
         for (int64_t r = 0; r < R; ++r) lr[(size_t)r] = c->h_len[(size_t)branch_of_row[(size_t)r]];
         FF_HIP(hipMalloc(&pl->d_len_rows, sizeof(double) * (size_t)std::max<int64_t>(R, 1)));

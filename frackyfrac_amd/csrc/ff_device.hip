@@ -103,6 +103,10 @@ void plan_free_device(ff_plan *pl)
     (void)hipFree(pl->d_Wl);
     (void)hipFree(pl->d_mlow);
     (void)hipFree(pl->d_low_tiles);
+    (void)hipFree(pl->d_low_entg);
+    (void)hipFree(pl->d_low_len);
+    (void)hipFree(pl->d_PR);
+    (void)hipFree(pl->d_glow);
     (void)hipFree(pl->d_indptr);
     (void)hipFree(pl->d_ids);
     (void)hipFree(pl->d_abnd);
@@ -403,9 +407,11 @@ int ff_plan_timing_collect_parts(ff_plan *pl, double *total_ms, double *rare_ms,
         if (hipEventSynchronize(pl->events[k].second) != hipSuccess ||
             hipEventElapsedTime(&ms, pl->events[k].first, pl->events[k].second) != hipSuccess)
             return FF_ERR_DEVICE;
-        // (the rare rows' kernel runs behind the matrix rows' in a weighted plan, ahead of them in an unweighted one)
-        if (parts && hipEventElapsedTime(&low, pl->mfma ? pl->events[k].first : pl->events[k].mid,
-                                         pl->mfma ? pl->events[k].mid : pl->events[k].second) != hipSuccess)
+        // (the rare rows' kernel runs behind the matrix rows' in a weighted plan, ahead of them in an unweighted or a
+        // generalized one)
+        const bool ahead = pl->mfma || pl->general;
+        if (parts && hipEventElapsedTime(&low, ahead ? pl->events[k].first : pl->events[k].mid,
+                                         ahead ? pl->events[k].mid : pl->events[k].second) != hipSuccess)
             return FF_ERR_DEVICE;
         sum += (double)ms;
         rare += (double)low;

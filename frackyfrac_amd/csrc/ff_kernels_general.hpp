@@ -103,11 +103,15 @@ G_DEFINE_USE(8)
 G_DEFINE_USE(16)
 
 // H x 64 tile per wave, one tile per wave, the full staged row range in order (the geometry of pair_exact64_skip_kernel).
-template <int KIND, int H>
+// SPLIT: the plan keeps its rare rows out of GT (ff_kernels_low_general.hpp); glow[slot] holds their (Mn, Md), PR[s] the
+// samples' quantised sums over them, and the epilogue adds (PR_i + PR_j - M) 2^-e -- an exact integer below 2^62, rounded
+// once -- to either sum before the division.  Without the flag the three trailing arguments are not read: today's code.
+template <int KIND, int H, bool SPLIT = false>
 G_F32 __global__ __launch_bounds__(256)
 void pair_general_kernel(const float2 *__restrict__ GT, int64_t ld, const double *__restrict__ branch_len, int64_t n_branches,
                          float am1, const XTile *__restrict__ tiles, int n_tiles, int64_t row_begin, int64_t row_end,
-                         int64_t slot_begin, double *__restrict__ out)
+                         int64_t slot_begin, double *__restrict__ out, const ulong2 *__restrict__ glow = nullptr,
+                         const unsigned long long *__restrict__ PR = nullptr, double inv_scale = 0.0)
 {
     static_assert(H - 1 <= G_VALUES_PAD, "the last staged row is read H - 1 cells past its end");
     const int lane = threadIdx.x & 63;
@@ -167,6 +171,12 @@ void pair_general_kernel(const float2 *__restrict__ GT, int64_t ld, const double
     for (int r = 0; r < H; ++r) {
         const int64_t i = tile.i0 + r;
         if (i < row_begin || i >= row_end || j >= i) continue;
+        if (SPLIT) {
+            const ulong2 m = glow[i * (i - 1) / 2 - slot_begin + j];
+            const unsigned long long both = PR[i] + PR[j];
+            a[r] += (double)(both - m.x) * inv_scale;
+            c[r] += (double)(both - m.y) * inv_scale;
+        }
         out[i * (i - 1) / 2 - slot_begin + j] = a[r] / c[r];  // (0 / 0 = NaN: two empty samples, as unifrac.go:204)
     }
 }

@@ -87,6 +87,12 @@ __global__ void stage_exact64_kernel(const int64_t *__restrict__ indptr,
 // binary64 and rounded once (alpha = 0: l itself).  A positive x under the smallest normal binary32 number is staged
 // as that number: the kernel's reciprocal, square root and logarithm instructions take no denormals, and presence is
 // what an abundance that small amounts to.
+__device__ __forceinline__ float2 general_cell(double x, double l, double alpha)
+{
+    const double p = alpha == 0.0 ? l : l * pow(x, alpha);
+    return make_float2(fmaxf((float)x, 1.17549435e-38f), (float)p);
+}
+// (a split plan's row_of holds -1 for a rare branch: its cells are the rare rows' entries, low_fill_general_kernel)
 __global__ void stage_general_kernel(const int64_t *__restrict__ indptr, const int32_t *__restrict__ branch_id,
                                      const double *__restrict__ abnd, const double *__restrict__ branch_len, double alpha,
                                      const int32_t *__restrict__ row_of, float2 *__restrict__ GT, int64_t ld)
@@ -97,9 +103,31 @@ __global__ void stage_general_kernel(const int64_t *__restrict__ indptr, const i
         const int32_t b = branch_id[t];
         const double x = abnd[t], l = branch_len[b];
         if (!(x > 0.0)) continue;  // (a flat node without abundance: the sample has not the branch)
-        const double p = alpha == 0.0 ? l : l * pow(x, alpha);
-        GT[(int64_t)(row_of ? row_of[b] : b) * ld + s] = make_float2(fmaxf((float)x, 1.17549435e-38f), (float)p);
+        const int64_t r = row_of ? row_of[b] : b;
+        if (r < 0) continue;
+        GT[r * ld + s] = general_cell(x, l, alpha);
     }
+}
+
+// The samples' totals of the staged one-sided terms over ALL rows, T_s = sum_b (binary32 p_s(b)), in binary64 by a fixed
+// tree of additions (the scale of gfix and the test that declines a split come from them: not from the launch).  One
+// workgroup per sample.
+__global__ __launch_bounds__(256)
+void general_totals_kernel(const int64_t *__restrict__ indptr, const int32_t *__restrict__ branch_id, const double *__restrict__ abnd,
+                           const double *__restrict__ branch_len, double alpha, double *__restrict__ total)
+{
+    __shared__ double part[256];
+    const int64_t s = blockIdx.x;
+    double mine = 0.0;
+    for (int64_t t = indptr[s] + threadIdx.x; t < indptr[s + 1]; t += blockDim.x)
+        if (abnd[t] > 0.0) mine += (double)general_cell(abnd[t], branch_len[branch_id[t]], alpha).y;
+    part[threadIdx.x] = mine;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) total[s] = part[0];
 }
 
 // Stage variance-adjusted weighted UniFrac (pair_vaw_kernel, ff_kernels_vaw.hpp), three kernels.
@@ -431,6 +459,26 @@ void low_fill_unw_kernel(const int64_t *__restrict__ indptr, const int32_t *__re
         if (r < 0) continue;
         const int64_t cell = (s / tile) * rows1 + r;
         entries[ptr[cell] + atomicAdd(&cursor[cell], 1u)] = (uint16_t)((uint32_t)(s % tile) << LOW_ROW_SHIFT);
+    }
+}
+
+// The same for a generalized plan (pair_low_general_kernel): an entry is (accumulator row's byte offset, x, q) with (x, p)
+// the cell stage_general_kernel would have put into GT and q = gfix(p, e); PR[s] (zeroed) gets the sample's sum of q.
+__global__ __launch_bounds__(256)
+void low_fill_general_kernel(const int64_t *__restrict__ indptr, const int32_t *__restrict__ branch_id,
+                             const double *__restrict__ abnd, const double *__restrict__ branch_len, double alpha, int e,
+                             const int32_t *__restrict__ low_of, int64_t rows1, int tile, const uint32_t *__restrict__ ptr,
+                             uint32_t *__restrict__ cursor, LowGEntry *__restrict__ entries, unsigned long long *__restrict__ PR)
+{
+    const int64_t s = blockIdx.x;
+    for (int64_t t = indptr[s] + threadIdx.x; t < indptr[s + 1]; t += blockDim.x) {
+        const int32_t b = branch_id[t], r = low_of[b];
+        if (r < 0) continue;
+        const int64_t cell = (s / tile) * rows1 + r;
+        const float2 c = general_cell(abnd[t], branch_len[b], alpha);
+        const uint64_t q = gfix(c.y, e);
+        entries[ptr[cell] + atomicAdd(&cursor[cell], 1u)] = LowGEntry{(uint32_t)(s % tile) << LOW_G_ROW_SHIFT, c.x, q};
+        atomicAdd(&PR[s], (unsigned long long)q);
     }
 }
 

@@ -5,7 +5,7 @@
 //   ff_dev_stage.hip   inputs -> HBM: stage A on the device, the flat nodes from the host, the choice of arithmetic,
 //                      branch compaction, the staged matrices / presence bits of every kernel
 //                      (ff_kernels_stage.hpp, ff_kernels_stage_a.hpp).
-//   ff_dev_run.hip     the pair kernels (ff_kernels_pair_sad / mfma / mfma_small / finish / exact_unw / exact_w / general / vaw.hpp), their work
+//   ff_dev_run.hip     the pair kernels (ff_kernels_pair_sad / mfma / mfma_small / finish / exact_unw / exact_w / general / low_general / vaw.hpp), their work
 //                      schedules per shard, the refinement queue and the audit, one pass of a plan.
 //
 // Every kernel lives in exactly one of the two files that launch kernels, inside its anonymous namespace (the
@@ -114,6 +114,15 @@ struct ff_plan {
     bool general = false;
     double g_alpha = 1.0;
     float2 *d_GT = nullptr;
+    // its rare rows (`split`; pair_low_general_kernel, blocks of LOW_G_TILE samples): the index and the bitmaps are
+    // d_low_ptr / d_low_bits / d_low_tiles above (the n_low_diag diagonal blocks first), d_GT and d_len_rows hold the
+    // matrix rows alone
+    ff::sched::LowGEntry *d_low_entg = nullptr;  // entries: (accumulator row, x, gfix(p))
+    float *d_low_len = nullptr;                  // the binary32 length by rare row
+    unsigned long long *d_PR = nullptr;          // [ld] the samples' sums of gfix(p) over the rare rows
+    ulong2 *d_glow = nullptr;                    // [slots of the shard] (Mn, Md): ff_kernels_low_general.hpp
+    int g_e = 0;                                 // gfix's scale
+    int n_low_diag = 0;
     // variance-adjusted weighted UniFrac (pair_vaw_kernel; `general` is set too: the same tiles, heights and shard
     // re-scheduling): d_GT holds the (x, c) plane, d_VB the (p, q) plane, d_VT per sample (T, 1 / T), all scaled
     bool vaw = false;

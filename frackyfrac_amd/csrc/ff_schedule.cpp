@@ -650,6 +650,12 @@ extern "C" int64_t ff_debug_tri_digits(const uint32_t *k, int64_t n, int8_t *out
     return ff::sched::TRI_KMAX;
 }
 
+// Diagnostics / tests: the quantiser of the generalized rare rows (gfix, ff_schedule.hpp) for n terms at the scale e.
+extern "C" void ff_debug_gfix(const float *t, int64_t n, int e, uint64_t *out)
+{
+    for (int64_t q = 0; q < n; ++q) out[q] = ff::sched::gfix(t[q], e);
+}
+
 // Diagnostics / tests: the schedule of a GRADED matrix-core sweep (build_mfma_schedule with duo_from_quad): items
 // as ff_debug_schedule returns them for FF_KERNEL_MFMA_I8.
 extern "C" int64_t ff_debug_graded_schedule(int64_t n_samples, int64_t slabs, int64_t row_begin, int64_t row_end, int n_cu,

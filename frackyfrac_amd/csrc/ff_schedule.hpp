@@ -7,6 +7,12 @@
 #include <utility>
 #include <vector>
 
+#if defined(__HIPCC__)
+#define FF_SCHED_HD __host__ __device__
+#else
+#define FF_SCHED_HD
+#endif
+
 namespace ff {
 namespace sched {
 
@@ -80,6 +86,45 @@ constexpr int LOW_UNW_LOAD = 8;
 constexpr int LOW_UNW_SPARE = 8;
 static_assert(LOW_UNW_LOAD * 2 == 16 && LOW_UNW_SPARE >= LOW_UNW_LOAD - 1, "the rare rows' spare entries must cover pair_low_unw_kernel's last load");
 inline int64_t low_unw_alloc_entries(int64_t n_entries) { return n_entries + LOW_UNW_SPARE; }
+// pair_low_general_kernel (generalized UniFrac: ff_kernels_low_general.hpp) owns 64 x 64 blocks of pairs, two uint64
+// accumulators a pair: 16 bytes, 1,024 a row, 64 KiB a block -- li * 1024 | lj * 16 is still one OR.  An entry is 16 bytes
+// (accumulator-row byte offset, x, q = gfix(p)); a step of the walk is LOW_G_LOAD entries, one 16-byte load each, from
+// wherever the list begins: a list's last step reads up to LOW_G_LOAD - 1 entries past the list's, and so the
+// array's, end.  The spare entries behind the array are zeros.
+// ONE wave per workgroup (two workgroups' accumulators fit a CU's LDS).  The frame's 16 waves on one block's accumulators
+// gave sums that changed from run to run on the device (every pair of a block, at any alpha, with the compiler's own
+// waits or explicit ones; the same code with one wave is exact and repeatable, and tools/microbench/lds_add64_rate.hip
+// finds ds_add_u64 itself exact under 16 waves' contention): the cause is not found, so the waves stay apart until it is.
+constexpr int LOW_G_THREADS = 64;
+constexpr int LOW_G_TILE = 64;
+constexpr int LOW_G_ROW_SHIFT = 10;  // li -> li * 64 * 16
+constexpr int LOW_G_COL_SHIFT = 6;   // li * 64 * 16 -> li * 16
+constexpr int LOW_G_LOAD = 2;
+constexpr int LOW_G_SPARE = 2;
+static_assert(LOW_G_SPARE >= LOW_G_LOAD - 1, "the rare rows' spare entries must cover pair_low_general_kernel's last step");
+static_assert(LOW_G_TILE << LOW_G_ROW_SHIFT == 65536 && LOW_G_ROW_SHIFT - LOW_G_COL_SHIFT == 4, "64 rows of 64 pairs of 16 bytes");
+inline int64_t low_g_alloc_entries(int64_t n_entries) { return n_entries + LOW_G_SPARE; }
+struct alignas(16) LowGEntry {
+    uint32_t off;  // the sample's accumulator row: li << LOW_G_ROW_SHIFT
+    float x;       // its staged abundance (the x of GT's cell)
+    uint64_t q;    // gfix(p), p the cell's one-sided term
+};
+static_assert(sizeof(LowGEntry) == 16, "an entry of pair_low_general_kernel is one 16-byte load");
+// The one quantiser of that path: the binary32 term t >= 0 times 2^e, truncated -- in integers, so that the staging
+// (host and device) and the kernel agree bit for bit.  The plan picks e so that a sample's whole sum of terms lies
+// below 2^61: a left shift never pushes a bit out (the clamps only keep the shifts defined).  (e in [-100, 210]: totals between the smallest binary32 denormal
+// and 2^31 terms of the largest number.)
+constexpr int G_FIX_TOP = 60;  // the largest per-sample total lands in [2^60, 2^61)
+FF_SCHED_HD inline uint64_t gfix(float t, int e)
+{
+    uint32_t u;
+    __builtin_memcpy(&u, &t, 4);
+    const int ex = (int)((u >> 23) & 255u);
+    const uint32_t m = (u & 0x7FFFFFu) | (ex ? 0x800000u : 0u);  // t = m 2^(max(ex, 1) - 150)
+    const int sh = (ex ? ex : 1) - 150 + e;
+    const int left = sh > 0 ? (sh < 63 ? sh : 63) : 0, right = sh < 0 ? (sh > -31 ? -sh : 31) : 0;
+    return (uint64_t)(m >> right) << left;
+}
 
 struct Item {        // one unit of work for a persistent wave: a pair tile over a
     int32_t i0, j0;  // branch range [k0, k1)

@@ -17,7 +17,7 @@ SWITCHES = [
     ("FF_COMPACT", "1", "tuning", "stage only the branches some sample touches"),
     ("FF_SPARSE", "1", "tuning", "the sparse-aware weighted kernel where enough (32-sample block, branch) cells are empty"),
     ("FF_SPARSE_MIN", "0.28", "tuning", "the share of empty cells from which the sparse-aware kernel is taken"),
-    ("FF_SPARSE_SPLIT", "unset", "tuning", "weighted FIXED32: 1 / 0 forces / forbids keeping the rows few samples reach out of the staged matrix and reducing them by pair_low_kernel over the pairs that both have them (unset: when that is estimated to save 30 % or more; same integers)"),
+    ("FF_SPARSE_SPLIT", "unset", "tuning", "weighted FIXED32: 1 / 0 forces / forbids keeping the rows few samples reach out of the staged matrix and reducing them by pair_low_kernel over the pairs that both have them (unset: when that is estimated to save 30 % or more; same integers); generalized d(alpha): 1 keeps them out of the (x, p) matrix and reduces them by pair_low_general_kernel in 64-bit integers (0 or unset: every row in the matrix -- forced only, until the kernel's costs are measured; declined where the quantisation could show)"),
     ("FF_UNW_SPLIT", "unset", "tuning", "unweighted FIXED32 on the matrix cores: 1 / 0 forces / forbids keeping the rows few samples reach out of the presence bits and adding their integer lengths by pair_low_unw_kernel to the pairs that both have them (unset: when that is estimated to save 7 % or more, for shards of a round of matrix-core tiles or more; a split plan never takes the small-shard kernel; same integers)"),
     ("FF_LOW_TILE", "unset", "tuning", "128 / 112 / 96 / 80 / 64 forces the side of pair_low_kernel's and pair_low_unw_kernel's blocks of pairs (unset: the one whose blocks fill their rounds of two workgroups per CU best)"),
     ("FF_REFINE", "1", "tuning", "FIXED32: exact re-computation of nearly equal pairs (0: tests of what it protects against)"),

@@ -131,6 +131,9 @@ typedef struct ff_options {
  * sums, every term non-negative, so that a distance is within (roundings per term + 2) * 2^-24 -- under 1e-6
  * ABSOLUTE -- of the formula above; a pair's value does not depend on tile height, shard or launch.  Such a plan
  * has nothing to refine or audit (ff_plan_refined_pairs and ff_plan_audit give zeros).
+ * On a sparse table FF_SPARSE_SPLIT=1 takes the rows few samples reach out of the matrix (ff_plan_info.rare_rows):
+ * their terms are summed over the pairs that both have them as 64-bit integers (the binary32 term times 2^e,
+ * truncated) and added before the division -- the same bound plus 2^-25, or the split is declined.
  * FF_ERR_ARG, before the device is touched: alpha NaN or outside [0, 1]; weighted == 0; FF_FLAG_UNSORTED_WALK (or
  * FF_L_REFERENCE) with it; a branch length or an abundance that is negative or not finite (the bound needs
  * non-negative terms). */
@@ -190,7 +193,8 @@ int ff_unifrac_dists(const ff_problem *p, const ff_options *o, double *out,
  * unifracDists as what it is in the reference: a LAZY, ORDERED sequence that stops computing when
  * its consumer stops (iter.Seq[float64], frcfrc/unifrac.go:209-228; early stop at :221-226).
  * The pair space of this shard (o->rank of o->world) is walked in sub-shards of at most
- * max_pairs_per_chunk distances (<= 0: 2^25 = 256 MB); each finished sub-shard is handed to
+ * max_pairs_per_chunk distances (<= 0: 2^25 = 256 MB; a generalized plan with rare rows keeps 16 bytes more per
+ * pair of a sub-shard on the device: 2^25 pairs = 512 MB); each finished sub-shard is handed to
  * `fn` as dists[0..n) = the distances of the consecutive global slots slot_begin .. slot_begin+n-1
  * (common.IterPairs order), sub-shards in ascending slot order, every slot exactly once.  The
  * buffer belongs to the library and is valid only during the call of fn.
@@ -275,10 +279,14 @@ typedef struct ff_plan_info {
     int64_t rare_rows;         /* FIXED32 on a sparse table: staged rows kept OUT of the matrix (few samples reach
                                   them) and reduced over the pairs that both have them -- by pair_low_kernel
                                   (weighted), by pair_low_unw_kernel ahead of the matrix cores (unweighted: `kernel`
-                                  stays FF_KERNEL_MFMA_I8); 0: none */
+                                  stays FF_KERNEL_MFMA_I8).  A generalized plan with FF_SPARSE_SPLIT=1: the rows kept
+                                  out of the (x, p) matrix and reduced by pair_low_general_kernel ahead of
+                                  pair_general_kernel (`kernel` stays FF_KERNEL_GENERAL_F32); a plan that declines the
+                                  split (the quantisation could show) reports 0.  0: none */
     double rare_updates;       /* that kernel's own work per pass: the sum over the rare rows of n_r (n_r - 1) / 2, n_r =
                                   the samples with a flat node on the row (weighted: an update = one min + one LDS add,
-                                  DESIGN 4.2; unweighted: one LDS add of the row's integer length).
+                                  DESIGN 4.2; unweighted: one LDS add of the row's integer length, DESIGN 4.10;
+                                  generalized: one power and two 64-bit LDS adds).
                                   A row shard's plan: the whole triangle's count times the shard's share of the pairs */
 } ff_plan_info;
 
@@ -303,7 +311,9 @@ typedef enum ff_kernel {
                                      :191-192 on a zero -- same bits as FF_KERNEL_EXACT_F64               */
     FF_KERNEL_GENERAL_F32 = 8,    /* pair_general_kernel: generalized UniFrac d(alpha), alpha != 1
                                      (FF_FLAG_GENERALIZED): a branch a row has not adds the column's own term
-                                     l y^alpha to both sums, one where both have it costs one power         */
+                                     l y^alpha to both sums, one where both have it costs one power; with
+                                     ff_plan_info.rare_rows > 0 pair_low_general_kernel reduces those rows
+                                     ahead of it                                                            */
     FF_KERNEL_VAW_F32 = 9         /* pair_vaw_kernel: variance-adjusted weighted UniFrac
                                      (FF_FLAG_VARIANCE_ADJUSTED): one reciprocal square root per term with at
                                      least one side present, the column's staged part times it where the row
