@@ -32,6 +32,7 @@ using namespace ff::sched;
 #include "ff_kernels_exact_w.hpp"
 #include "ff_kernels_general.hpp"
 #include "ff_kernels_vaw.hpp"
+#include "ff_kernels_vaw_skip.hpp"
 #include "ff_kernels_low.hpp"
 #include "ff_kernels_low_unw.hpp"
 #include "ff_kernels_low_general.hpp"
@@ -317,6 +318,16 @@ int launch_general(ff_plan *pl, hipStream_t st, double *d_out, hipEvent_t ev_mid
     if (pl->n_xtiles <= 0) return FF_OK;
     if (!g_tile_height_ok(pl->x_tile_h)) return ff::fail(FF_ERR_INTERNAL, err, errlen, "generalized: no kernel for tile height %d", pl->x_tile_h);
     const bool h8 = pl->x_tile_h == 8;
+    if (pl->vaw && pl->vaw_skip) {  // its row-skipping form: the occupancy streams in place of the row count
+        if (pl->x_tile_h != VW_SKIP_TILE_H) return ff::fail(FF_ERR_INTERNAL, err, errlen, "variance adjusted: no skipping kernel for tile height %d", pl->x_tile_h);
+        pair_vaw_skip_kernel<VW_SKIP_TILE_H><<<dim3((unsigned)((pl->n_xtiles + 3) / 4)), dim3(256), 0, st>>>(pl->d_GT, pl->d_VB, pl->d_VT, inf.ld,
+                                                                            pl->d_len_rows ? pl->d_len_rows : pl->d_len,
+                                                                            (pl->xu_slabs + XU_OCC_LOAD - 1) / XU_OCC_LOAD, pl->d_xu_rowocc,
+                                                                            pl->d_xu_colocc, pl->xu_occ_stride, pl->d_xtiles, pl->n_xtiles,
+                                                                            inf.row_begin, inf.row_end, inf.slot_begin, d_out);
+        FF_HIP(hipGetLastError());
+        return FF_OK;
+    }
     if (pl->vaw) {  // variance-adjusted weighted UniFrac: the same tiles, its own planes
         auto vkern = h8 ? pair_vaw_kernel<8> : pair_vaw_kernel<16>;
         vkern<<<dim3((unsigned)((pl->n_xtiles + 3) / 4)), dim3(256), 0, st>>>(pl->d_GT, pl->d_VB, pl->d_VT, inf.ld,
@@ -450,6 +461,33 @@ int upload_exact64_tiles(ff_plan *pl, int h, char *err, size_t errlen)
     FF_HIP(hipMalloc(&pl->d_xtiles, sizeof(XTile) * std::max<size_t>(xt.size(), 1)));
     if (!xt.empty()) FF_HIP(hipMemcpy(pl->d_xtiles, xt.data(), sizeof(XTile) * xt.size(), hipMemcpyHostToDevice));
     inf.n_wave_slots = (int64_t)xt.size();
+    // Variance-adjusted UniFrac: the row-skipping form (pair_vaw_skip_kernel) on the same tiles.  What it would do is
+    // counted exactly, on the device: the visited (tile, row) cells by kind, the (tile, slab) cells that are not empty, the
+    // chain-Y rows run where the column group is empty.  FF_VAW_SKIP=1 takes it (and stages the occupancy words), 0
+    // forbids it, and unset keeps the dense form: the per-cell costs of the kinds are not measured yet, and without them
+    // there is no estimate to follow (not borrowed from pair_exact_unw_skip_kernel's).
+    pl->vaw_skip = false;
+    inf.active_fraction = 1.0;
+    if (pl->vaw && pl->d_xu_rowocc && !xt.empty() && h == VW_SKIP_TILE_H && env_int("FF_VAW_SKIP", -1) == 1) {
+        static_assert(X_TILE_J == 64, "pair_vaw_skip_kernel: a column group is a tile's columns");
+        if (xt[0].i0 % VW_OCC_ROW_GROUP != 0 || h % VW_OCC_ROW_GROUP != 0)
+            return ff::fail(FF_ERR_INTERNAL, err, errlen, "variance adjusted: a tile at row %d of height %d is not whole row groups", xt[0].i0, h);
+        Scratch<unsigned long long> counts;
+        FF_HIP(counts.alloc(VS_CNT_N));
+        FF_HIP(hipMemset(counts.p, 0, sizeof(unsigned long long) * VS_CNT_N));
+        vw_visit_count_kernel<<<dim3((unsigned)xt.size()), dim3(64)>>>(pl->d_xtiles, h, pl->d_xu_rowocc, pl->d_xu_colocc, pl->xu_occ_stride,
+                                                                      pl->d_Xbits, pl->xu_ldx, pl->xu_slabs, counts.p);
+        FF_HIP(hipGetLastError());
+        unsigned long long cnt[VS_CNT_N];
+        FF_HIP(hipMemcpy(cnt, counts.p, sizeof(cnt), hipMemcpyDeviceToHost));
+        const double cells = (double)xt.size() * (double)inf.n_rows;
+        const double visited = (double)cnt[VS_CNT_BOTH] + (double)cnt[VS_CNT_COL_EMPTY] + (double)cnt[VS_CNT_ROW_EMPTY];
+        pl->vaw_skip = true;
+        inf.active_fraction = cells > 0 ? visited / cells : 0.0;
+        inf.n_items = (int64_t)cnt[VS_CNT_SLABS];  // the (tile, slab) cells the walk stops at
+        // terms issued: H rows a cell where the lanes have their own operands, the chain-Y rows alone where they have not
+        inf.elements = (double)X_TILE_J * ((double)h * ((double)cnt[VS_CNT_BOTH] + (double)cnt[VS_CNT_ROW_EMPTY]) + (double)cnt[VS_CNT_Y_ROWS]);
+    }
     return FF_OK;
 }
 
@@ -571,6 +609,8 @@ int schedule_exact64(ff_plan *pl, char *err, size_t errlen)
                 }
             }
         }
+        // (pair_vaw_skip_kernel exists at one height: a plan that is told to take it gets that height, unless one is forced)
+        if (pl->vaw && pl->d_xu_rowocc && env_int("FF_VAW_SKIP", -1) == 1) h = VW_SKIP_TILE_H;
         for (int cand : X_TILE_HEIGHTS)
             if (cand == forced && (!pl->general || g_tile_height_ok(cand))) h = forced;
         pl->x_tile_h = h;

@@ -1215,6 +1215,29 @@ int stage_for_vaw(StageCtx &x, char *err, size_t errlen)
         FF_HIP(hipGetLastError());
         FF_HIP(hipDeviceSynchronize());  // (tot goes out of scope)
     }
+    // The row-skipping form (pair_vaw_skip_kernel): a presence word per (slab of XU_SLAB staged rows, sample) -- kept for
+    // the count of what a shard's tiles would visit -- and from them the occupancy words of every row group and every
+    // column group, [group][xu_occ_stride], zero behind the last slab.  They do not depend on the shard.  Staged where the
+    // form can be taken: FF_VAW_SKIP=1 (unset keeps the dense form until there is an estimate to follow).
+    if (env_int("FF_VAW_SKIP", -1) == 1 && vw_occ_col_groups(ld) <= 65535) {
+        pl->xu_slabs = (int)xu_slabs(R);
+        pl->xu_ldx = ld;
+        pl->xu_occ_stride = xu_occ_stride(R);
+        const size_t bits_bytes = sizeof(uint32_t) * (size_t)pl->xu_slabs * (size_t)ld;
+        const size_t row_bytes = sizeof(uint32_t) * (size_t)vw_occ_row_groups(ld) * (size_t)pl->xu_occ_stride;
+        const size_t col_bytes = sizeof(uint32_t) * (size_t)vw_occ_col_groups(ld) * (size_t)pl->xu_occ_stride;
+        inf.staged_bytes += (double)bits_bytes + (double)row_bytes + (double)col_bytes;
+        FF_ALLOC(pl->d_Xbits, bits_bytes, "the presence bits");
+        FF_ALLOC(pl->d_xu_rowocc, row_bytes, "the row groups' occupancy words");
+        FF_ALLOC(pl->d_xu_colocc, col_bytes, "the column groups' occupancy words");
+        FF_HIP(hipMemset(pl->d_Xbits, 0, bits_bytes));
+        FF_HIP(hipMemset(pl->d_xu_rowocc, 0, row_bytes));
+        FF_HIP(hipMemset(pl->d_xu_colocc, 0, col_bytes));
+        if (N > 0 && nnz > 0) stage_vaw_bits_kernel<<<dim3((unsigned)N), dim3(256)>>>(d_indptr, d_ids, d_abnd, row_of.p, pl->d_Xbits, ld);
+        xu_occupancy_kernel<<<dim3((unsigned)pl->xu_slabs, (unsigned)vw_occ_col_groups(ld)), dim3(64)>>>(pl->d_Xbits, ld, pl->xu_occ_stride,
+                                                                                                       pl->d_xu_rowocc, pl->d_xu_colocc);
+        FF_HIP(hipGetLastError());
+    }
     if (row_of.p) {  // treeDists by staged row
         std::vector<double> lr((size_t)R);
         for (int64_t r = 0; r < R; ++r) lr[(size_t)r] = c->h_len[(size_t)branch_of_row[(size_t)r]];

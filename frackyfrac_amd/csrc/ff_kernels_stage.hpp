@@ -197,6 +197,21 @@ __global__ void stage_vaw_kernel(const int64_t *__restrict__ indptr, const int32
     }
 }
 
+// (4) stage_vaw_bits_kernel, a block per sample, for pair_vaw_skip_kernel (ff_kernels_vaw_skip.hpp): bit (row % XU_SLAB) of
+// word [row / XU_SLAB][s] where stage_vaw_kernel wrote a cell with x != 0 -- the same test of the same flat node.  The
+// occupancy words per row group and per column group are xu_occupancy_kernel's over these words.
+__global__ void stage_vaw_bits_kernel(const int64_t *__restrict__ indptr, const int32_t *__restrict__ branch_id,
+                                      const double *__restrict__ abnd, const int32_t *__restrict__ row_of,
+                                      uint32_t *__restrict__ Xb, int64_t ldx)
+{
+    const int64_t s = blockIdx.x;
+    for (int64_t t = indptr[s] + threadIdx.x; t < indptr[s + 1]; t += blockDim.x) {
+        if (!(abnd[t] > 0.0)) continue;
+        const int32_t b = branch_id[t], row = row_of ? row_of[b] : b;
+        atomicOr(&Xb[(int64_t)(row / XU_SLAB) * ldx + s], 1u << (row % XU_SLAB));
+    }
+}
+
 // W_s = sum_b q_s(b): grid (ld/64, row chunks), one column per lane.
 __global__ void colsum_kernel(const uint32_t *__restrict__ QT, int64_t ld, int64_t rows,
                               int64_t rows_per_block, unsigned long long *__restrict__ W)

@@ -5,7 +5,7 @@
 //   ff_dev_stage.hip   inputs -> HBM: stage A on the device, the flat nodes from the host, the choice of arithmetic,
 //                      branch compaction, the staged matrices / presence bits of every kernel
 //                      (ff_kernels_stage.hpp, ff_kernels_stage_a.hpp).
-//   ff_dev_run.hip     the pair kernels (ff_kernels_pair_sad / mfma / mfma_small / finish / exact_unw / exact_w / general / low_general / vaw.hpp), their work
+//   ff_dev_run.hip     the pair kernels (ff_kernels_pair_sad / mfma / mfma_small / finish / exact_unw / exact_w / general / low_general / vaw / vaw_skip.hpp), their work
 //                      schedules per shard, the refinement queue and the audit, one pass of a plan.
 //
 // Every kernel lives in exactly one of the two files that launch kernels, inside its anonymous namespace (the
@@ -127,6 +127,9 @@ struct ff_plan {
     // re-scheduling): d_GT holds the (x, c) plane, d_VB the (p, q) plane, d_VT per sample (T, 1 / T), all scaled
     bool vaw = false;
     float2 *d_VB = nullptr, *d_VT = nullptr;
+    // its row-skipping form (pair_vaw_skip_kernel): d_Xbits, xu_ldx (= info.ld), xu_slabs, d_xu_rowocc, d_xu_colocc and
+    // xu_occ_stride below hold ITS presence and occupancy words (ff_schedule.hpp VW_OCC_*; null with FF_VAW_SKIP=0)
+    bool vaw_skip = false;  // the shard's tiles run the skipping form (chosen per schedule: FF_VAW_SKIP)
     bool walk = false;  // FF_FLAG_UNSORTED_WALK: no staging at all, pair_walk_kernel over the flat nodes as they stand
     // EXACT64 unweighted (pair_exact_unw_kernel): presence bits, lengths by staged row, tiles
     bool xu = false;

@@ -172,6 +172,21 @@ static_assert(64 % XU_TILE_H == 0, "a 64-sample column group holds whole row gro
 constexpr double XU_NS_DENSE_ROW = 0.0456;
 constexpr double XU_NS_SKIP_ROW = 0.0532;
 constexpr double XU_NS_SKIP_SLAB = 0.0111;
+//   pair_vaw_skip_kernel<H> (variance-adjusted UniFrac, tiles of H x X_TILE_J pairs, H one of G_TILE_HEIGHTS) walks the same
+//   streams -- XU_SLAB, XU_OCC_LOAD, XU_OCC_PAD_CHUNKS, xu_occ_chunks and xu_occ_stride as above -- over ITS samples-per-row
+//   ld = round_up(N, X_TILE_J): one word per VW_OCC_ROW_GROUP-sample row group and one per X_TILE_J-sample column group.  A
+//   tile of two row groups ORs two words; its first row is a multiple of its height (build_tiles), so of the group size.
+constexpr int VW_OCC_ROW_GROUP = XU_TILE_H;  // (xu_occupancy_kernel forms both kinds of word)
+static_assert(X_TILE_J == 64 && X_TILE_J % VW_OCC_ROW_GROUP == 0, "a column group of pair_vaw_skip_kernel is one wave's lanes and holds whole row groups");
+static_assert(G_TILE_HEIGHTS[0] % VW_OCC_ROW_GROUP == 0 && G_TILE_HEIGHTS[1] % VW_OCC_ROW_GROUP == 0 && G_TILE_HEIGHTS[1] <= 2 * VW_OCC_ROW_GROUP,
+              "pair_vaw_skip_kernel: a tile's rows are one or two whole row groups");
+//   Built at ONE height: with 16 rows the two operand sets (64 scalar registers of row cells) leave the walk's masks and
+//   pointers no room -- 277 scalar spills and two waves per SIMD in the compiler's report.  Bits do not
+//   depend on the height.
+constexpr int VW_SKIP_TILE_H = 8;
+static_assert(VW_SKIP_TILE_H == G_TILE_HEIGHTS[0], "pair_vaw_skip_kernel's height is one of pair_vaw_kernel's");
+inline int64_t vw_occ_row_groups(int64_t ld) { return ld / VW_OCC_ROW_GROUP; }
+inline int64_t vw_occ_col_groups(int64_t ld) { return ld / X_TILE_J; }
 struct XUTile {
     int32_t i0, j0;  // rows i0 .. i0 + XU_TILE_H - 1, columns j0 + 64 t + lane, t < jn
     int32_t jn;      // 64-sample column groups: 1 or 2 (the last tile of a row block may be the narrower one)

@@ -25,6 +25,7 @@ SWITCHES = [
     ("FF_EXACT_UNW", "1", "tuning", "EXACT64 unweighted on pair_exact_unw_kernel (0: the weighted kernel's arithmetic on presence as 1.0 / 0.0; same bits, three times the time)"),
     ("FF_XU_JMAX", "unset", "tuning", "1 / 2 forces the width of pair_exact_unw_kernel's tiles in 64-sample column groups (unset: 2, 1 for shards of fewer than six such tiles per CU)"),
     ("FF_XU_SKIP", "unset", "tuning", "EXACT64 unweighted: 1 / 0 forces / forbids pair_exact_unw_skip_kernel, which runs only the branches some sample of a pair tile has (unset: when the exact count of the (tile, branch) and (tile, slab) cells it would visit puts it 7 % or more under the dense form; 0 also stages no occupancy words; same bits)"),
+    ("FF_VAW_SKIP", "unset", "tuning", "variance-adjusted UniFrac: 1 takes pair_vaw_skip_kernel (8-row tiles), which runs only the branches some sample of a pair tile has and, where only the tile's rows or only its columns have one, neither the loads nor the rows that add +0.0 (0 or unset: pair_vaw_kernel on every row -- forced only, until the per-cell costs are measured, and only 1 stages the occupancy words; same bits)"),
     ("FF_X_SKIP", "1", "tuning", "EXACT64 weighted on pair_exact64_skip_kernel, which takes the reference's shortcut for branches a row has not (0: pair_exact64_kernel, six operations for every term; same bits)"),
     ("FF_X_TILE_H", "by size", "tuning", "rows of a weighted EXACT64 pair tile: 4, 8, 10, 12, 14 or 16 (any height: same bits)"),
     ("FF_GATHER", "auto", "tuning", "multi-GPU gather transport: ipc (copies into rank 0's mapped array) / nccl (RCCL send / recv); auto: ipc when it can be set up and is fast enough"),

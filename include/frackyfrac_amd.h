@@ -151,7 +151,9 @@ typedef struct ff_options {
  * The entry points that flatten (ff_unifrac, ff_plan_create_from_leaves, frcfrc -w -vaw) flatten undivided and
  * sorted under this flag whatever `leave_unnormalized` says.  The plan runs pair_vaw_kernel (FF_KERNEL_VAW_F32,
  * reported precision FF_PRECISION_FLOAT32): binary32 terms, binary64 sums, within 1e-6 ABSOLUTE of the formula; a
- * pair's value does not depend on tile height, shard or launch; nothing to refine or audit.
+ * pair's value does not depend on tile height, shard or launch; nothing to refine or audit.  On a sparse table the
+ * tuning switch FF_VAW_SKIP=1 takes pair_vaw_skip_kernel instead, which runs only the branches some sample of a pair
+ * tile has: the same bits (ff_plan_info.active_fraction).
  * FF_ERR_ARG, before the device is touched: weighted == 0; FF_FLAG_GENERALIZED, FF_FLAG_UNSORTED_WALK or
  * FF_L_REFERENCE with it; a precision other than FF_PRECISION_AUTO; a branch length or an abundance that is
  * negative or not finite. */
@@ -275,7 +277,9 @@ typedef struct ff_plan_info {
                                   FF_KERNEL_EXACT_F64_UNW: share of the shard's (pair tile, staged row) cells in which some
                                   sample of the tile has the branch, when the row-skipping form runs (it visits those and
                                   no others; `elements` counts the terms it issues, `n_items` the (tile, 32-row slab) cells
-                                  that are not empty); 1 on the dense form.  1 where not counted */
+                                  that are not empty); 1 on the dense form.
+                                  FF_KERNEL_VAW_F32: the same three fields in the same way when pair_vaw_skip_kernel
+                                  runs (FF_VAW_SKIP=1, 8-row tiles); exactly 1 on pair_vaw_kernel.  1 where not counted */
     int64_t rare_rows;         /* FIXED32 on a sparse table: staged rows kept OUT of the matrix (few samples reach
                                   them) and reduced over the pairs that both have them -- by pair_low_kernel
                                   (weighted), by pair_low_unw_kernel ahead of the matrix cores (unweighted: `kernel`
@@ -317,7 +321,10 @@ typedef enum ff_kernel {
     FF_KERNEL_VAW_F32 = 9         /* pair_vaw_kernel: variance-adjusted weighted UniFrac
                                      (FF_FLAG_VARIANCE_ADJUSTED): one reciprocal square root per term with at
                                      least one side present, the column's staged part times it where the row
-                                     has not the branch                                                     */
+                                     has not the branch; or, with the tuning switch FF_VAW_SKIP=1, its
+                                     row-skipping form pair_vaw_skip_kernel, which leaves out the branches
+                                     none of a tile's samples has and the loads and rows that only add +0.0
+                                     (same bits; active_fraction < 1 says it runs)                          */
 } ff_kernel;
 
 /* Stage: quantise / densify the flat nodes into the branch-major matrix in HBM
